@@ -41,6 +41,13 @@ gathered to rank 0 (the FAPI rank) over RCCL once per step. Strong scaling (--sh
 split across the ranks (srsgpu.dist.shard_ues); rank 0 holds the cell's samples and runs its OFDM stages, the resource
 grids are exchanged by subcarrier band (srsgpu.dist.GridExchange), each rank runs the upper PHY of its UEs, and the TBs
 are gathered the same way. One JSON line from rank 0.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) builds the input sets, warms up, captures the graphs, times
+exactly N steps and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/dl_samples.npy, ul_tbs.npy, ul_tb_ok.npy; the
+inputs are seeded, so two builds can be compared output for output). Everything else runs only with `--full`, after
+the headline: the UL payload check, the decoder roofline and per-stage passes, the extra operating points and
+workloads, and the reference CPU leg with the UL LLR parity check.
 """
 import argparse
 import ctypes
@@ -246,13 +253,47 @@ class InputSet:
         self.tb_gather = None   # srsgpu.dist.TbGather of this set (ranks > 1)
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6  # all files of one --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, st, rank):
+    """--dump-outputs: what a caller of the timed path receives from the step that input set `st` ran last, as float32
+    .npy files: the DL baseband samples of every DL slot group (interleaved re / im), the decoded UL TB bytes and the
+    TB CRC flags. The TBs and flags are written whole; the sample arrays share what is left of DUMP_MAX_BYTES, and
+    one that does not fit is reduced to a fixed sample (ascending indices drawn with seed 0, the same for every run
+    of the same shape). Called after the timed loop's device synchronise."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    small = {"ul_tbs": st.ul.d_tbs, "ul_tb_ok": st.ul.d_tb_ok}
+    left = DUMP_MAX_BYTES
+    for name, t in small.items():
+        a = t.cpu().numpy().astype(np.float32)
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    share = max(left, 0) // 4 // len(st.dls)  # float32 elements per sample array
+    for j, d in enumerate(st.dls):
+        a = d.d_samples.cpu().numpy().astype(np.float32, copy=False)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, f"dl_samples{'_%d' % j if j else ''}{suffix}.npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # A minimum: the headline loop is extended until it has run for --min-time seconds (the actual count is reported).
-    ap.add_argument("--steps", type=int, default=4000)
-    ap.add_argument("--min-time", type=float, default=1.0, help="seconds the headline timed loop runs at least")
+    ap.add_argument("--steps", type=int, default=4000, help="timed steps of the headline loop (exactly this many)")
+    ap.add_argument("--min-time", type=float, default=1.0,
+                    help="--full: the extra operating points and workloads are timed for at least half of this many "
+                         "seconds (their loops are extended; the counts are reported)")
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: UL payload check, decoder "
+                         "roofline and per-stage passes, the extra operating points and workloads, the reference CPU "
+                         "leg with the UL LLR parity check. A plain run sets up, warms up, times --steps steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (DL baseband samples, decoded "
+                         "UL TBs, TB CRC flags) as DIR/<name>.npy")
     ap.add_argument("--profile", choices=sorted(PROFILES), default="ref")
     ap.add_argument("--workload", choices=["multi_ue", "testmode"], default="multi_ue")
     # testmode: 4 TDD periods per step (40 slots, 0.18 ms); MI355X sweep: 2 periods 142.7k (5 sets) / 159.2k (3 sets),
@@ -312,10 +353,12 @@ def _load_keyed(path, wl_key):
     return j.get("by_workload", {}).get(wl_key)
 
 
-def measure(args, env):
-    """One workload / profile measured end to end: build the input sets, warm up, capture, the timed loop (extended to
-    --min-time), roofline of the dominant kernel, operating points, and (rank 0, one GPU) the reference CPU leg with
-    the UL LLR parity check. Returns the result dict (rank 0's is printed)."""
+def measure(args, env, primary=True):
+    """One workload / profile measured end to end: build the input sets, warm up, capture and the timed loop (exactly
+    --steps steps for the primary measurement, which also writes --dump-outputs; a secondary one is extended to
+    --min-time). With --full also the UL payload check, roofline of the dominant kernel, operating points, and
+    (rank 0, one GPU) the reference CPU leg with the UL LLR parity check. Returns the result dict (rank 0's is
+    printed)."""
     prof = PROFILES[args.profile]
     ctx, dev, gen, world, rank = env["ctx"], env["dev"], env["gen"], env["world"], env["rank"]
     S = args.slots_per_step
@@ -554,11 +597,43 @@ def measure(args, env):
             it_all.append(np.where(it > 0, it, args.iterations))
         return float(np.concatenate(ok_all).mean()), float(np.concatenate(it_all).mean())
 
-    steps, elapsed = timed_min(args.steps, args.min_time)
-    tb_success, avg_iters = ul_results(not args.worst_case)
+    def release():
+        """Release the working sets (graphs first) before another workload is measured in the same process."""
+        for st in sets:
+            st.graph = st.graph_back = st.graph_ul = None
+        sets.clear()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+
+    if primary:
+        steps, elapsed = args.steps, timed(args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, sets[(steps - 1) % K], rank)
+    else:
+        steps, elapsed = timed_min(args.steps, args.min_time)
     agg = world if args.shard == "cells" else 1  # ranks whose slots add up (weak scaling)
     step_rate = agg * steps / elapsed            # steps/s of the whole job
     value = slots_per_step * step_rate
+    result = {
+        "metric": "PDSCH+PUSCH slots/sec (100MHz 4x4) + LDPC info-bits/s at 1/2/4/8 GPU",
+        "value": value,
+        "unit": "slots/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / steps,
+        "higher_is_better": True,
+        "scaling": "weak" if args.shard == "cells" else "strong",
+        "vs_baseline": None,
+        "dtype": "int8/bf16/f32",
+        "full": args.full,
+    }
+    if skip:
+        result["INVALID_timing_experiment_skipped_stages"] = skip
+    if not args.full:
+        release()
+        return result
+    tb_success, avg_iters = ul_results(not args.worst_case)
 
     # Roofline kernel time: an eager pass over the sets with the decoder plans' own stage events (the decoding launch
     # on its stream), right after the timed loop.
@@ -681,18 +756,7 @@ def measure(args, env):
         workload = (f"n78 100 MHz 4x4 slot, 273 PRB, 64 UEs x 4-5 PRB, 256QAM MCS27, DM-RS symbols 2+11; "
                     f"DL 4 layers, UL {prof['ul_desc']}; LDPC BG1")
 
-    result = {
-        "metric": "PDSCH+PUSCH slots/sec (100MHz 4x4) + LDPC info-bits/s at 1/2/4/8 GPU",
-        "value": value,
-        "unit": "slots/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / steps,
-        "higher_is_better": True,
-        "scaling": "weak" if args.shard == "cells" else "strong",
-        "vs_baseline": None,
-        "dtype": "int8/bf16/f32",
+    result.update({
         "data": ("synthetic: random TB payloads; PUSCH input = " +
                  ("Gaussian noise samples (no TB ever valid: all LDPC iterations)" if args.worst_case else
                   f"UL TBs through a GPU UE transmitter (same encoder / DM-RS / modulator), a random unitary 4x4 "
@@ -755,9 +819,7 @@ def measure(args, env):
                              "not HBM-bound (DESIGN.md)"},
         "roofline_valu": valu,
         "cpu_baseline": None,
-    }
-    if skip:
-        result["INVALID_timing_experiment_skipped_stages"] = skip
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         n_dl, n_ul = len(dl_segs), len(ul_segs)
         tb_host = st0.dl_tbs[: sum(dl.tb_bytes[:n_dl])].cpu().numpy()
@@ -786,12 +848,7 @@ def measure(args, env):
                 "over_one_step": int(np.sum(d > 1)),
                 "reference_build_spread": reference_build_spread(ul_ues, samples_host, ul_cell.slot_index(0),
                                                                  ref_llr)}
-    # Release the working sets (graphs first) before another workload is measured in the same process.
-    for st in sets:
-        st.graph = st.graph_back = st.graph_ul = None
-    del sets
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
+    release()
     return result
 
 
@@ -823,9 +880,10 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
+    torch.manual_seed(1234 + rank)  # testmode's fresh DL payloads come from the default generator
     env = {"ctx": srsgpu.Context(local_rank), "dev": dev, "gen": gen, "world": world, "rank": rank}
     result = measure(args, env)
-    if args.extra_workloads and not args.worst_case:
+    if args.full and args.extra_workloads and not args.worst_case:
         result["workloads"] = {}
         for name, over in EXTRA_WORKLOADS:
             if over["workload"] == "testmode" and args.shard == "ues" and world > 1:
@@ -838,7 +896,7 @@ def main():
             a.min_time = args.min_time / 2
             a.cpu_seconds = args.cpu_seconds / 2
             a.no_cpu_baseline = args.no_cpu_baseline or a.profile != "ref"  # the reference estimates one layer
-            result["workloads"][name] = summary(measure(a, env))
+            result["workloads"][name] = summary(measure(a, env, primary=False))
     if rank == 0:
         print(json.dumps(result))
     if dist.is_initialized():

@@ -5,8 +5,8 @@
 #   tests            GPU parity suite (pytest -m gpu)
 #   tests:EXPR       GPU tests selected by pytest -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (default shape) -> bench.json
-#   bench_driver     python bench.py --steps 20 --warmup 5 -> bench_driver.json
+#   bench            python bench.py --full (default shape, every leg) -> bench.json
+#   bench_driver     python bench.py --steps 20 --warmup 5 (a plain run: the headline only) -> bench_driver.json
 #   slots1 / slots16 tools/processor_bench.py --only-slots at 1 / 16 threads (SRSGPU_BATCH_TIMING=1)
 #   slots16ul        the same, UL only
 #   slotslat         UL slot processors at 16 threads, free-running and paced at real time (500 us per slot and
@@ -14,7 +14,7 @@
 #   dulowul          tools/du_low_bench.py, UL only, sector group with 13 symbols in flight, 4/6/8 sectors (latency)
 #   slots_trace16    the same at 16 threads
 #   slots_trace      rocprofv3 kernel + memory-copy trace of the slot processors at one thread (UL)
-#   kstats           rocprofv3 --kernel-trace --stats of the default bench
+#   kstats           rocprofv3 --kernel-trace --stats of the default bench (--full)
 #   lower            tools/lower_phy_bench.py with the multi-sector sweep
 #   lower_trace      rocprofv3 kernel trace of the sector group at 8 sectors
 #   dulow            tools/du_low_bench.py: lower PHY + PUSCH service per sector, paced, 1..8 sectors
@@ -49,7 +49,7 @@ for step in "$@"; do
         || { cat "$OUT/smoke.log"; exit 1; }
       cat "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
       tail -c 600 "$OUT/bench.json" ;;
     bench_driver)
       timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" \
@@ -83,7 +83,7 @@ for step in "$@"; do
         tools/processor_bench.py --only-slots --threads 1 --repetitions 1 --slots 30 --directions ul \
         > "$OUT/slots_trace.log" 2>&1 || { tail -20 "$OUT/slots_trace.log"; exit 1; } ;;
     kstats)
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/kstats" -o k -- python3 -u bench.py \
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/kstats" -o k -- python3 -u bench.py --full \
         > "$OUT/kstats_bench.json" 2> "$OUT/kstats.log" || { tail -20 "$OUT/kstats.log"; exit 1; } ;;
     lower)
       echo "cgroup cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null || echo n/a), nproc $(nproc)"
@@ -110,7 +110,7 @@ for step in "$@"; do
       rm -rf "$OUT/pmc_lds"
       cat "$OUT/pmc_lds.txt" | cut -c1-400 ;;
     traffic)
-      PB="--no-cpu-baseline --no-extra-points --no-extra-workloads --steps 40 --warmup 4 --min-time 0"
+      PB="--full --no-cpu-baseline --no-extra-points --no-extra-workloads --steps 40 --warmup 4 --min-time 0"
       timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv \
         -- python3 -u bench.py $PB > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err" || { tail -20 "$OUT/pmc_fetch.err"; exit 1; }
       timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv \
@@ -148,7 +148,7 @@ for step in "$@"; do
       for i in $(seq 1 "$N"); do
         for v in default alt; do
           if [ "$v" = default ]; then E=(); else E=("${VARS[@]}"); fi
-          env "${E[@]}" timeout -k 10 300 python -u bench.py > "$OUT/benchab_${v}_$i.json" 2> "$OUT/benchab_${v}_$i.err" \
+          env "${E[@]}" timeout -k 10 300 python -u bench.py --full > "$OUT/benchab_${v}_$i.json" 2> "$OUT/benchab_${v}_$i.err" \
             || { tail -20 "$OUT/benchab_${v}_$i.err"; exit 1; }
           python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], round(d['value']), [round(p['value']) for p in d['operating_points']], round(d['stage_ms_per_step']['pusch_decode'], 4), {k: round(v['value']) for k, v in d.get('workloads', {}).items()})" \
             "$OUT/benchab_${v}_$i.json" "$v ${E[*]}"
@@ -191,7 +191,7 @@ for step in "$@"; do
       SPEC=${step#ab:}; DIR=${SPEC%%:*}; N=2; [[ "$SPEC" == *:* ]] && N=${SPEC##*:}
       for i in $(seq 1 "$N"); do
         for lib in lib "$DIR"; do
-          SRSGPU_LIB=srsran-5g_amd/$lib/libsrsgpu_phy.so timeout -k 10 300 python -u bench.py \
+          SRSGPU_LIB=srsran-5g_amd/$lib/libsrsgpu_phy.so timeout -k 10 300 python -u bench.py --full \
             > "$OUT/ab_${lib}_$i.json" 2> "$OUT/ab_${lib}_$i.err" || { tail -20 "$OUT/ab_${lib}_$i.err"; exit 1; }
           python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], round(d['value']), d.get('stage_ms_per_step', ''))" \
             "$OUT/ab_${lib}_$i.json" "$lib"

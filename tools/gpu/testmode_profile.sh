@@ -4,7 +4,7 @@ OUT=gpurun_out/${1:-testmode}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$(pwd)
-timeout -k 10 300 python bench.py --workload testmode --snr-db 30 --point-steps 1000 --cpu-seconds 8 \
+timeout -k 10 300 python bench.py --full --workload testmode --snr-db 30 --point-steps 1000 --cpu-seconds 8 \
   > "$OUT/bench_testmode.json" 2> "$OUT/bench_testmode.err"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/$OUT/tm_stats" -o run --output-format csv -- \
   python3 "$R/bench.py" --workload testmode --snr-db 30 --steps 40 --warmup 4 --no-extra-points --no-cpu-baseline \

@@ -74,7 +74,11 @@ typedef enum {
   SRSGPU_OPTION_ENCODER_BYTE_KERNEL = 4,
   /** 0 (default) / 1: the PDSCH encoder clears its codeword output before every execution (0: only when its
    *  codeblocks do not each store whole words that tile the output). */
-  SRSGPU_OPTION_ENCODER_ZERO_OUTPUT = 5
+  SRSGPU_OPTION_ENCODER_ZERO_OUTPUT = 5,
+  /** 1 (default) / 0: a PUSCH decoder plan whose transport blocks all have one codeblock, every one dematched by the
+   *  decoder itself, has the decoder kernel write the transport blocks and their CRC flags and skips the TB-stage
+   *  launch (0: always the separate TB stage). */
+  SRSGPU_OPTION_DECODER_TB_FOLD = 6
 } srsgpu_option;
 
 /** Sets option `option` (srsgpu_option) of a context for the plans created afterwards. */

@@ -102,6 +102,10 @@ struct srsgpu_pusch_decoder_plan {
   tb_slice*             d_slices   = nullptr;  ///< Sliced TB stage (large segmented TBs): pusch_tb_slice_kernel.
   uint32_t*             d_tb_acc   = nullptr;  ///< Per-TB CRC sums and slice counters (zero between executes).
   int                   nof_slices = 0;
+  /// Every TB has one codeblock and every codeblock runs in a fused one-codeblock decoder launch: the decoder writes the
+  /// TBs and their flags (launch_ldpc_decode_pk d_tbs) and execute launches no TB stage
+  /// (SRSGPU_OPTION_DECODER_TB_FOLD).
+  bool                  fold_tb    = false;
 };
 
 struct srsgpu_ldpc_decoder_plan {
@@ -491,6 +495,8 @@ int* context_option(srsgpu_context* ctx, int option)
       return &ctx->opt_encoder_byte_kernel;
     case SRSGPU_OPTION_ENCODER_ZERO_OUTPUT:
       return &ctx->opt_encoder_zero_output;
+    case SRSGPU_OPTION_DECODER_TB_FOLD:
+      return &ctx->opt_decoder_tb_fold;
     default:
       return nullptr;
   }
@@ -826,7 +832,10 @@ int execute_decoder_plan(const srsgpu_ldpc_decoder_plan* plan,
                          hipStream_t                     s,
                          const int8_t*                   d_cw_llrs  = nullptr,
                          int8_t*                         d_harq     = nullptr,
-                         int8_t* const*                  d_harq_cbs = nullptr)
+                         int8_t* const*                  d_harq_cbs = nullptr,
+                         uint8_t*                        d_tbs      = nullptr,  // TB fold (srsgpu_pusch_decoder_plan::fold_tb:
+                                                                                // every group a fused one-codeblock launch)
+                         uint8_t*                        d_tb_crc_ok = nullptr)
 {
   for (const auto& g : plan->groups) {
     if (g.pack == 2) {
@@ -838,13 +847,17 @@ int execute_decoder_plan(const srsgpu_ldpc_decoder_plan* plan,
                                plan->ctx->d_pair_ab2[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, s, d_harq_cbs,
                                g.d_dm, g.d_dm != nullptr ? d_harq : nullptr);
     } else if (g.packed) {
+      // The edge-split kernel's CRC check takes a half's columns from its first lane: a half must be whole waves.
+      if (g.split == 2 && g.threads % 128 != 0) {
+        return fail(SRSGPU_ERR_INVALID_ARG, "edge-split decoder group of %d threads (not a multiple of 128)", g.threads);
+      }
       if (g.d_dm != nullptr && (d_cw_llrs == nullptr || (d_harq == nullptr && d_harq_cbs == nullptr))) {
         return fail(SRSGPU_ERR_INVALID_ARG, "fused decoder group without codeword LLRs / HARQ buffer");
       }
       launch_ldpc_decode_pk(g.bg, plan->impl, g.max_layers, g.split, g.d_desc, g.count, g.threads,
                             g.d_dm != nullptr ? d_cw_llrs : d_llrs, d_out, d_nof_iterations,
                             plan->ctx->d_pair_ab[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, g.d_dm,
-                            g.d_dm != nullptr ? d_harq : nullptr, s, d_harq_cbs);
+                            g.d_dm != nullptr ? d_harq : nullptr, s, d_harq_cbs, d_tbs, d_tb_crc_ok);
     } else {
       launch_ldpc_decode(g.bg, plan->impl, g.d_desc, g.count, g.threads, d_llrs, d_out, d_nof_iterations,
                          plan->ctx->d_shifts32[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, s, d_harq_cbs);
@@ -859,6 +872,7 @@ struct pusch_cb_params {
   bool     new_data, early_stop;
   float    sf;
   uint32_t Nref, E, llr_offset, harq_offset, out_offset, cb_index;
+  uint32_t tb_index = 0, tb_offset = 0, tb_bytes = 0;  ///< The codeblock's transport block (TB-level plans; TB fold).
 };
 
 /// Validates one PUSCH codeblock (ldpc_rate_dematcher_impl.cpp:54-:99 plus the decoder's checks) and appends its
@@ -913,6 +927,9 @@ int add_pusch_cb(srsgpu_context*        ctx,
   d.Qm          = static_cast<uint8_t>(qm);
   d.new_data    = c.new_data ? 1 : 0;
   d.cb_index    = c.cb_index;
+  d.tb_index    = c.tb_index;
+  d.tb_offset   = c.tb_offset;
+  d.tb_bytes    = c.tb_bytes;
   const uint64_t R = c.E / static_cast<uint32_t>(qm);
   d.r_magic        = ((1ULL << 40) + R - 1) / R;
   // A first transmission from rv 0 of the whole circular buffer that reaches every systematic position without
@@ -1432,6 +1449,9 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
                         c.scaling_factor, c.Nref, static_cast<uint32_t>(cb.E),
                         c.llr_offset + static_cast<uint32_t>(cb.cw_offset),
                         c.harq_offset + static_cast<uint32_t>(i) * static_cast<uint32_t>(N), ci * CB_MSG_STRIDE, ci};
+      p.tb_index  = t;
+      p.tb_offset = c.tb_offset;
+      p.tb_bytes  = static_cast<uint32_t>(seg.tbs) / 8u;
       int r = add_pusch_cb(ctx, ci, p, batch, dms);
       if (r != SRSGPU_OK) {
         return r;
@@ -1479,11 +1499,23 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
       }
     }
   }
-  int r         = upload_pusch_cb_plan(ctx, impl, batch, dms, &plan->cbs);
+  // TB fold: with one codeblock per TB the TB stage only copies the head of the message and the codeblock's flag. When
+  // every codeblock is also dematched by a one-codeblock decoder launch (none left for the separate dematcher, no
+  // two-codeblock workgroups) none can take the already-decoded skip path, so every launch reaches a point where the
+  // flag is known: the decoder writes both and the TB stage is not launched (srsgpu_pusch_decoder_plan_assemble
+  // still runs it on request).
+  int r = upload_pusch_cb_plan(ctx, impl, batch, dms, &plan->cbs);
   if (r != SRSGPU_OK) {
     delete plan;
     return r;
   }
+  // Decided from the launches the plan really holds: every group a fused one-codeblock packed launch.
+  const auto& groups = plan->cbs->dec->groups;
+  plan->fold_tb      = ctx->opt_decoder_tb_fold != 0 && nof_tbs > 0 && dms.empty() &&
+                  std::all_of(tbs.begin(), tbs.end(), [](const tb_dec_desc& t) { return t.nof_cbs == 1; }) &&
+                  std::all_of(groups.begin(), groups.end(), [](const srsgpu_ldpc_decoder_plan::group& g) {
+                    return g.packed && g.pack == 1 && g.d_dm != nullptr;
+                  });
   if (nof_tbs > 0 && (hipMalloc(&plan->d_tb, tbs.size() * sizeof(tb_dec_desc)) != hipSuccess ||
                       hipMemcpy(plan->d_tb, tbs.data(), tbs.size() * sizeof(tb_dec_desc), hipMemcpyHostToDevice) !=
                           hipSuccess)) {
@@ -1552,14 +1584,16 @@ int execute_pusch_decoder_plan(const srsgpu_pusch_decoder_plan* plan,
   stage_timer::mark(ev, 1, s);
   stage_timer::mark(evd, 0, s);
   int r = execute_decoder_plan(plan->cbs->dec, d_harq, d_cb_msgs, d_cb_nof_iterations, d_cb_crc_ok, s, d_llrs, d_harq,
-                               d_harq_cbs);
+                               d_harq_cbs, plan->fold_tb ? d_tbs : nullptr, plan->fold_tb ? d_tb_crc_ok : nullptr);
   if (r != SRSGPU_OK) {
     return r;
   }
   stage_timer::mark(evd, 1, s);
   stage_timer::mark(ev, 2, s);
-  launch_plan_tb_stage(plan, d_cb_crc_ok, d_cb_msgs, d_tbs, d_tb_crc_ok, s);
-  HIP_TRY(hipGetLastError());
+  if (!plan->fold_tb) {
+    launch_plan_tb_stage(plan, d_cb_crc_ok, d_cb_msgs, d_tbs, d_tb_crc_ok, s);
+    HIP_TRY(hipGetLastError());
+  }
   stage_timer::mark(ev, 3, s);
   return SRSGPU_OK;
 }

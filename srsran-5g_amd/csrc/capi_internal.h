@@ -85,6 +85,7 @@ struct srsgpu_context {
   int opt_decoder_fused_dematch = 1;
   int opt_encoder_byte_kernel   = 0;
   int opt_encoder_zero_output   = 0;
+  int opt_decoder_tb_fold       = 1;
   std::mutex                           mtx;
 };
 

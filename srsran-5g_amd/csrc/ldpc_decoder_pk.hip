@@ -439,27 +439,128 @@ __device__ __forceinline__ uint32_t pair_pos(uint32_t l, uint32_t H)
   return (l < H) ? 2u * l : 2u * (l - H) + 1u;
 }
 
-/// Hard decisions of the K*Z systematic bits, packed MSB first (log_likelihood_ratio.cpp:350 hard_decision).
+/// Byte offset of position l (0 <= l < Z) of slot i within a column of an image that interleaves the pairs of PKN
+/// codeblocks (the two-codeblock workgroups below; PKN = 1, i = 0 is pair_pos).
+template <int PKN>
+__device__ __forceinline__ uint32_t pair_pos_pkn(uint32_t l, uint32_t H, uint32_t i)
+{
+  return ((l < H) ? 2u * PKN * l : 2u * PKN * (l - H) + 1u) + 2u * i;
+}
+
+/// The four int8 values of a dword clamped to +/-64 at once. A byte is outside [-64, 63] exactly when its two top bits
+/// differ (01xxxxxx: 64 .. 127, 10xxxxxx: -128 .. -65); it then keeps its sign bit, gets bit 6 set and its low six bits
+/// cleared: 0x40 = 64 or 0xc0 = -64 (64 itself maps to itself).
+__device__ __forceinline__ uint32_t clamp64_x4(uint32_t w)
+{
+  const uint32_t x = (w ^ (w << 1)) & 0x80808080u;  // bit 7 of every byte to clamp
+  const uint32_t a = x >> 1;                        // its bit 6
+  const uint32_t m = a - (x >> 7);                  // its low six bits (0x40 - 0x01: no borrow between bytes)
+  return (w & ~m) | a;
+}
+
+/// Fused dematching, four consecutive input positions k .. k + 3 (the bytes of w, lowest first) into slot `slot` of the
+/// soft-bit image. Requires k a multiple of 4, k + 3 < full (whole lifted columns: the +/-64 clamp, and every position
+/// counts for the trailing-zero trim) and Z a multiple of 8: Z and H are then multiples of 4, so the four positions lie
+/// in one column and one half of it, 2 PKN bytes apart. One division, one pair position and one clamp for the group
+/// instead of one per byte; `last` takes the group's highest non-zero position.
+template <int PKN>
+__device__ __forceinline__ void soft_put_x4(int8_t* __restrict__ soft,
+                                            uint32_t w,
+                                            uint32_t k,
+                                            uint32_t Z,
+                                            uint32_t H,
+                                            uint32_t magic,
+                                            uint32_t slot,
+                                            int&     last)
+{
+  const uint32_t cq  = __umulhi(k, magic);
+  const uint32_t l   = k - __umul24(cq, Z);
+  int8_t*        dst = soft + __umul24(cq + 2u, PKN * SOFT_COL_STRIDE) + pair_pos_pkn<PKN>(l, H, slot);
+  const uint32_t c   = clamp64_x4(w);
+  dst[0]             = static_cast<int8_t>(c);
+  dst[2 * PKN]       = static_cast<int8_t>(c >> 8);
+  dst[4 * PKN]       = static_cast<int8_t>(c >> 16);
+  dst[6 * PKN]       = static_cast<int8_t>(c >> 24);
+  const int top      = static_cast<int>(k) + ((31 - __clz(static_cast<int>(w))) >> 3);
+  last               = (w != 0u && top > last) ? top : last;
+}
+
+/// Hard decisions of the systematic bits 8 b .. 8 b + 7 (those below nbits), MSB first, for any Z: one division for the
+/// byte, then the position walks on, into the next column where the byte straddles one.
+template <int PKN>
+__device__ __forceinline__ uint32_t hard_byte(const int8_t* __restrict__ soft,
+                                              uint32_t b,
+                                              uint32_t nbits,
+                                              uint32_t Z,
+                                              uint32_t H,
+                                              uint32_t magic,
+                                              uint32_t slot)
+{
+  const uint32_t i0   = 8u * b;
+  const uint32_t col  = __umulhi(i0, magic);
+  uint32_t       l    = i0 - col * Z;
+  const int8_t*  cp   = soft + col * (PKN * SOFT_COL_STRIDE);
+  uint32_t       byte = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 8; ++k) {
+    if (i0 + k < nbits) {
+      byte |= static_cast<uint32_t>(cp[pair_pos_pkn<PKN>(l, H, slot)] <= 0) << (7u - k);
+    }
+    ++l;
+    if (l == Z) {
+      l = 0;
+      cp += PKN * SOFT_COL_STRIDE;
+    }
+  }
+  return byte;
+}
+
+/// Bit 7 of every byte of p that is <= 0 as an int8: the sign bit, or low seven bits of zero (0x80 - low7 keeps bit 7
+/// only then; no borrow between bytes).
+__device__ __forceinline__ uint32_t le0_x4(uint32_t p)
+{
+  return ((0x80808080u - (p & 0x7f7f7f7fu)) | p) & 0x80808080u;
+}
+
+/// Hard decisions of the K*Z systematic bits, packed MSB first (log_likelihood_ratio.cpp:350 hard_decision). The
+/// first nbytes2 bytes also go to out2 (the transport block of a single-codeblock TB; nbytes2 = 0: none).
+/// Z a multiple of 16: the 8 positions of an output byte lie in one column and one half of it (Z and H are multiples
+/// of 8), a 16-byte aligned run of the image in which they are the even (lower half) or odd (upper half) bytes: one
+/// 16-byte LDS read, two v_perm that gather the 8 values, the <= 0 tests of four bytes at a time, and shifts that
+/// line the 8 flags up. Other Z: hard_byte.
 __device__ __forceinline__ void write_hard_bits_pk(const int8_t* __restrict__ soft,
                                                    uint8_t* __restrict__ out,
                                                    int      nbits,
                                                    int      Z,
-                                                   uint32_t magic)
+                                                   uint32_t magic,
+                                                   uint8_t* __restrict__ out2    = nullptr,
+                                                   int                   nbytes2 = 0)
 {
   const uint32_t H      = static_cast<uint32_t>(Z) / 2u;
   const int      nbytes = (nbits + 7) / 8;
+  const bool     z16    = (Z & 15) == 0;
   for (int b = threadIdx.x; b < nbytes; b += blockDim.x) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int i = 8 * b + k;
-      if (i < nbits) {
-        const uint32_t col = __umulhi(static_cast<uint32_t>(i), magic);
-        const uint32_t l   = static_cast<uint32_t>(i) - col * static_cast<uint32_t>(Z);
-        byte |= static_cast<uint32_t>(soft[col * SOFT_COL_STRIDE + pair_pos(l, H)] <= 0) << (7 - k);
-      }
+    uint32_t byte;
+    if (z16) {
+      const uint32_t i0  = 8u * static_cast<uint32_t>(b);
+      const uint32_t col = __umulhi(i0, magic);
+      const uint32_t l   = i0 - __umul24(col, static_cast<uint32_t>(Z));
+      const bool     up  = l >= H;
+      const uint32_t off = __umul24(col, SOFT_COL_STRIDE) + 2u * (up ? l - H : l);
+      const uint4    v   = *reinterpret_cast<const uint4*>(soft + off);
+      const uint32_t sel = up ? 0x07050301u : 0x06040200u;
+      const uint32_t f0  = le0_x4(__builtin_amdgcn_perm(v.y, v.x, sel));  // positions 0 .. 3 in bytes 0 .. 3
+      const uint32_t f1  = le0_x4(__builtin_amdgcn_perm(v.w, v.z, sel));  // positions 4 .. 7
+      const uint32_t q   = f0 | (f1 >> 4);  // byte i: bit 7 position i, bit 3 position 4 + i; each to bit 7 - position
+      byte               = (q | (q >> 9) | (q >> 18) | (q >> 27)) & 0xffu;
+    } else {
+      byte = hard_byte<1>(soft, static_cast<uint32_t>(b), static_cast<uint32_t>(nbits), static_cast<uint32_t>(Z), H,
+                          magic, 0u);
     }
     out[b] = static_cast<uint8_t>(byte);
+    if (b < nbytes2) {
+      out2[b] = static_cast<uint8_t>(byte);
+    }
   }
 }
 
@@ -480,7 +581,9 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
                                                              uint8_t* __restrict__ cb_crc_ok,
                                                              const dm_desc* __restrict__ dms,
                                                              int8_t* __restrict__ harq,
-                                                             int8_t* const* __restrict__ harq_cbs)
+                                                             int8_t* const* __restrict__ harq_cbs,
+                                                             uint8_t* __restrict__ tbs,
+                                                             uint8_t* __restrict__ tb_crc_ok)
 {
   using G = bg_t<BG>;
   // Only the first K + MAXL columns can be touched by MAXL layers: the soft-bit image shrinks with the layer bound
@@ -496,6 +599,9 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
   DEC_STAMP(0);
   DEC_PROF(29, __builtin_amdgcn_s_memrealtime());
   const dec_desc d = descs[blockIdx.x];
+  // Single-codeblock transport blocks written by the decoder (launch_ldpc_decode_pk d_tbs): fused launches only, whose
+  // codeblocks cannot take the already-decoded skip path below.
+  const bool fold_tb = FUSE && tb_crc_ok != nullptr;
   if constexpr (FUSE) {
     // New data invalidates the codeblock CRC flag of the HARQ context (pusch_decoder_impl.cpp:132).
     if (cb_crc_ok != nullptr && threadIdx.x == 0) {
@@ -576,6 +682,7 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
     const bool q8 = Qm == 8 && ((dm.llr_offset & 7u) == 0u);
     const bool q8x4 = q8 &&
                       ((R | ninfo | Fl | static_cast<int>(reinterpret_cast<uintptr_t>(hb))) & 3) == 0;
+    const bool z8 = (Z & 7) == 0;
     if (q8x4) {
       for (int r0 = 4 * static_cast<int>(threadIdx.x); r0 < R; r0 += 4 * static_cast<int>(blockDim.x)) {
         uint2 v[4];
@@ -592,11 +699,18 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
             w |= byte << (8 * q);
           }
           const int n = j * R + r0;  // n .. n + 3 on one side of ninfo (both multiples of 4)
-          const int k = n < ninfo ? n : n + Fl;
+          const int k = n < ninfo ? n : n + Fl;  // a multiple of 4
           *reinterpret_cast<uint32_t*>(hb + k) = w;
+          // The four positions as a group (soft_put_x4) when Z is a multiple of 8, per byte for other Z. The test
+          // against `full` is defensive: every plan the host builds gives a fused codeblock whole lifted columns
+          // (capi.cpp add_pusch_cb: n_llr a multiple of Z, E + F <= n_llr), so no group reaches a partial column.
+          if (z8 && static_cast<uint32_t>(k) + 4u <= full) {
+            soft_put_x4<1>(soft, w, static_cast<uint32_t>(k), static_cast<uint32_t>(Z), H, d.div_magic, 0u, last);
+          } else {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
+            for (int q = 0; q < 4; ++q) {
+              soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
+            }
           }
         }
       }
@@ -773,6 +887,9 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
     }
     if (threadIdx.x == 0) {
       results[d.cb_index] = -1;
+      if (fold_tb) {
+        tb_crc_ok[dms[blockIdx.x].tb_index] = 0;
+      }
     }
     return;
   }
@@ -793,6 +910,9 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
     // The host bound is derived from the same input length: cannot happen; fail loudly rather than decode wrongly.
     if (threadIdx.x == 0) {
       results[d.cb_index] = -2;
+      if (fold_tb) {
+        tb_crc_ok[dms[blockIdx.x].tb_index] = 0;
+      }
     }
     return;
   }
@@ -879,36 +999,44 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
       uint32_t acc  = 0;
       uint32_t zero = 0;
       if (active) {
-        // Opaque copies again: per-column table offsets would otherwise be hoisted out of the iteration loop. The
-        // table loads are unconditional (index clamped, value masked): no divergent branches between them, all of
-        // a chunk's loads in flight at once, saddr form (global base in SGPRs + 32-bit byte offset).
+        // Opaque copies again: per-column table addresses would otherwise be hoisted out of the iteration loop. The
+        // table loads are unconditional (positions < K Z, value masked): no divergent branches between them, all of
+        // a chunk's loads in flight at once, saddr form: the column's table base c Z is scalar arithmetic (SGPRs), the
+        // lane adds its two constant byte offsets 4 z and 4 (z + H).
         uint32_t zz   = static_cast<uint32_t>(z);
         uint32_t ZZ   = static_cast<uint32_t>(Z);
         uint32_t HH   = H;
         asm volatile("" : "+v"(zz));
         asm volatile("" : "+s"(ZZ), "+s"(HH));
-        // SPLIT = 2: half 0 sums the first K / 2 columns, half 1 the rest (hcol = half x K / 2).
+        // SPLIT = 2: half 0 sums the first K / 2 columns, half 1 the rest (hcol = half x K / 2; a half is whole waves,
+        // launch_ldpc_decode_pk, so hcol is wave-uniform).
         constexpr int KC   = (SPLIT == 2) ? G::K / 2 : G::K;
-        const int     hcol = half * KC;
-        uint32_t      ia   = zz + static_cast<uint32_t>(hcol) * ZZ;
-        const int8_t* scol = soft + hcol * SOFT_COL_STRIDE;
+        const int     hcol = (SPLIT == 2) ? __builtin_amdgcn_readfirstlane(half) * KC : 0;
+        const auto*   tcol = reinterpret_cast<const uint8_t*>(crc_table + static_cast<uint32_t>(hcol) * ZZ);
+        const uint32_t oa  = 4u * zz;
+        const uint32_t ob  = 4u * (zz + HH);
+        const int8_t* scol = soft + hcol * SOFT_COL_STRIDE + 2u * zz;
+        // Both rows' soft bits are one 16-bit pair: one LDS read per column. zmin: the unsigned minimum over the
+        // columns of the two bytes (each in its own 16-bit half): 0 in a half when a soft bit was zero.
+        uint32_t zsel = 0x0c010c00u;
+        asm volatile("" : "+s"(zsel));
+        u16x2 zmin = uu(0xff);
         static_for<KC>([&](auto Ci) {
           constexpr int  c  = decltype(Ci)::value;
-          const uint32_t ib = ia + HH;
-          const int      sa = scol[c * SOFT_COL_STRIDE + 2 * zz];
-          const int      sb = scol[c * SOFT_COL_STRIDE + 2 * zz + 1];
-          zero |= static_cast<uint32_t>(sa == 0) | static_cast<uint32_t>(sb == 0);
-          // ia, ib < K Z: positions past the message (fillers) read the table's zero tail (get_crc_table).
-          const uint32_t ta = crc_table[ia];
-          const uint32_t tb = crc_table[ib];
-          acc ^= (sa <= 0) ? ta : 0u;
-          acc ^= (sb <= 0) ? tb : 0u;
-          ia += ZZ;
+          const int      ps = *reinterpret_cast<const int16_t*>(scol + c * SOFT_COL_STRIDE);
+          zmin = __builtin_elementwise_min(zmin, as_u16(__builtin_amdgcn_perm(0u, static_cast<uint32_t>(ps), zsel)));
+          // Positions past the message (fillers) read the table's zero tail (get_crc_table).
+          const uint8_t* tc = tcol + static_cast<size_t>(4u * (static_cast<uint32_t>(c) * ZZ));
+          const uint32_t ta = *reinterpret_cast<const uint32_t*>(tc + oa);
+          const uint32_t tb = *reinterpret_cast<const uint32_t*>(tc + ob);
+          acc ^= (static_cast<int8_t>(ps) <= 0) ? ta : 0u;  // row z: the low byte
+          acc ^= (ps < 256) ? tb : 0u;                      // row z + H: the high byte <= 0
           // Bound the table loads in flight (each holds a result register).
           if constexpr (c % CRC_CHUNK == CRC_CHUNK - 1) {
             __builtin_amdgcn_sched_barrier(0);
           }
         });
+        zero = (zmin.x == 0 || zmin.y == 0) ? 1u : 0u;
       }
       acc      = wave_xor(acc);
       zero     = (__ballot(zero != 0) != 0) ? 1u : 0u;
@@ -926,7 +1054,17 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
       const bool early = (d.flags & DEC_FLAG_EARLY_STOP) != 0;
       DEC_STAMP(3 + 2 * (it & 7));
       if ((tzero == 0 || !early) && tacc == 0) {
-        write_hard_bits_pk(soft, cb_out, msg_len, Z, d.div_magic);
+        if (fold_tb) {
+          // The codeblock is its transport block (pusch_tb.hip, one codeblock: the TB CRC is the codeblock CRC and the
+          // TB is the head of the message), so the bytes and the flag go out from here.
+          const dm_desc dm = dms[blockIdx.x];
+          write_hard_bits_pk(soft, cb_out, msg_len, Z, d.div_magic, tbs + dm.tb_offset, static_cast<int>(dm.tb_bytes));
+          if (threadIdx.x == 0) {
+            tb_crc_ok[dm.tb_index] = 1;
+          }
+        } else {
+          write_hard_bits_pk(soft, cb_out, msg_len, Z, d.div_magic);
+        }
         DEC_STAMP(28);
         DEC_PROF(30, __builtin_amdgcn_s_memrealtime());
         if (threadIdx.x == 0) {
@@ -944,6 +1082,9 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
   DEC_PROF(30, __builtin_amdgcn_s_memrealtime());
   if (threadIdx.x == 0) {
     results[d.cb_index] = -1;
+    if (fold_tb) {
+      tb_crc_ok[dms[blockIdx.x].tb_index] = 0;  // the TB bytes stay as they are (pusch_tb.hip)
+    }
   }
 }
 
@@ -973,13 +1114,6 @@ struct pk_geom {
   static constexpr int RED          = 2 * PKN * WAVES * 2;     ///< CRC reduction ints: [parity][slot][wave][acc, zero]
   static constexpr int SCRATCH_INTS = WAVES + RED + 2 * PKN;
 };
-
-/// Byte offset of position l (0 <= l < Z) of slot i within a column of the interleaved image.
-template <int PKN>
-__device__ __forceinline__ uint32_t pair_pos_pkn(uint32_t l, uint32_t H, uint32_t i)
-{
-  return ((l < H) ? 2u * PKN * l : 2u * PKN * (l - H) + 1u) + 2u * i;
-}
 
 /// LLRs of one codeblock -> its slot of the interleaved image (ldpc_decoder_impl.cpp:152; the plain kernel's load with
 /// the slot's addresses), the punctured columns and every position beyond the input zeroed. Returns this thread's
@@ -1098,18 +1232,11 @@ __device__ __forceinline__ void write_hard_bits_pkn(const int8_t* __restrict__ s
 {
   const uint32_t H      = static_cast<uint32_t>(Z) / 2u;
   const int      nbytes = (nbits + 7) / 8;
+  // One division per output byte (hard_byte); the interleaved image spreads a byte's 8 positions over 32 bytes, so
+  // the one-codeblock kernel's single 16-byte read does not carry over.
   for (int b = static_cast<int>(z); b < nbytes; b += static_cast<int>(H)) {
-    uint32_t byte = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int i = 8 * b + k;
-      if (i < nbits) {
-        const uint32_t col = __umulhi(static_cast<uint32_t>(i), magic);
-        const uint32_t l   = static_cast<uint32_t>(i) - col * static_cast<uint32_t>(Z);
-        byte |= static_cast<uint32_t>(soft[col * pk_geom<PKN>::CS + pair_pos_pkn<PKN>(l, H, slot)] <= 0) << (7 - k);
-      }
-    }
-    out[b] = static_cast<uint8_t>(byte);
+    out[b] = static_cast<uint8_t>(hard_byte<PKN>(soft, static_cast<uint32_t>(b), static_cast<uint32_t>(nbits),
+                                                 static_cast<uint32_t>(Z), H, magic, slot));
   }
 }
 
@@ -1147,6 +1274,7 @@ __device__ __forceinline__ int load_fused_pkn(int8_t* __restrict__ soft, const i
   const bool q8   = Qm == 8 && ((dm.llr_offset & 7u) == 0u);
   const bool q8x4 = q8 &&
                     ((R | ninfo | Fl | static_cast<int>(reinterpret_cast<uintptr_t>(hb))) & 3) == 0;
+  const bool z8   = (Z & 7) == 0;
   if (q8x4) {
     for (int r0 = 4 * static_cast<int>(threadIdx.x); r0 < R; r0 += 4 * static_cast<int>(blockDim.x)) {
       uint2 v[4];
@@ -1164,9 +1292,14 @@ __device__ __forceinline__ int load_fused_pkn(int8_t* __restrict__ soft, const i
         const int n = j * R + r0;
         const int k = n < ninfo ? n : n + Fl;
         *reinterpret_cast<uint32_t*>(hb + k) = w;
+        // As the one-codeblock kernel: the group of four inside the whole lifted columns, else per byte.
+        if (z8 && static_cast<uint32_t>(k) + 4u <= full) {
+          soft_put_x4<PKN>(soft, w, static_cast<uint32_t>(k), static_cast<uint32_t>(Z), H, d.div_magic, slot, last);
+        } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
+          for (int q = 0; q < 4; ++q) {
+            soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
+          }
         }
       }
     }
@@ -1483,18 +1616,24 @@ void launch_ldpc_decode_pk(int             bg,
                            const dm_desc*  d_dm,
                            int8_t*         d_harq,
                            hipStream_t     stream,
-                           int8_t* const*  d_harq_cbs)
+                           int8_t* const*  d_harq_cbs,
+                           uint8_t*        d_tbs,
+                           uint8_t*        d_tb_crc_ok)
 {
   if (nof_cbs <= 0) {
     return;
   }
   dim3 grid(nof_cbs), block(block_threads);
   const bool fuse = d_dm != nullptr;
+  // The TB fold needs the dm_desc's TB fields: fused launches only.
+  uint8_t* tb_ok = (fuse && d_tbs != nullptr) ? d_tb_crc_ok : nullptr;
 #define SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, SPLIT_)                                                                   \
   (fuse ? ldpc_decode_pk_kernel<BG_, MODE_, MAXL_, SPLIT_, true><<<grid, block, 0, stream>>>(                          \
-              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, d_dm, d_harq, d_harq_cbs)            \
+              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, d_dm, d_harq, d_harq_cbs, d_tbs,     \
+              tb_ok)                                                                                                   \
         : ldpc_decode_pk_kernel<BG_, MODE_, MAXL_, SPLIT_, false><<<grid, block, 0, stream>>>(                         \
-              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, nullptr, nullptr, d_harq_cbs))
+              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, nullptr, nullptr, d_harq_cbs,         \
+              nullptr, nullptr))
 #define SRSGPU_PK_LAUNCH(BG_, MODE_, MAXL_)                                                                            \
   (split == 2 ? SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, 2) : SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, 1))
   if (bg == 1) {

@@ -52,9 +52,12 @@ struct dm_desc {
   uint8_t  Qm;           ///< Modulation order.
   uint8_t  new_data;     ///< First transmission: copy instead of combine.
   uint32_t cb_index;     ///< Codeblock index (CRC flag slot).
+  uint32_t tb_index;     ///< TB fold (launch_ldpc_decode_pk d_tbs): the flag slot of the codeblock's transport block,
+  uint32_t tb_offset;    ///< its first byte in the TB buffer
+  uint32_t tb_bytes;     ///< and its size: the first tb_bytes bytes of the decoded message.
   uint64_t r_magic;      ///< ceil(2^40 / (E / Qm)): exact n / R as (n * r_magic) >> 40 for n < 2^20.
 };
-static_assert(sizeof(dm_desc) == 48, "dm_desc layout");
+static_assert(sizeof(dm_desc) == 56, "dm_desc layout");
 
 /// CRC job of one transport block (tb_crc_kernel).
 struct tb_crc_desc {
@@ -239,7 +242,12 @@ int debug_read_decoder_profile_pk(uint64_t* dst, size_t n);
 
 /// Launches the packed two-rows-per-lane LDPC decoder (ldpc_decoder_pk.hip; even Z, block_threads >= Z / 2, or
 /// >= 2 x 64 ceil(Z / 128) with split = 2) built for at most max_layers layers (8, 16 or all; every codeblock of the
-/// launch must satisfy layers_bound() <= it). split = 2: each row's edges are shared by two halves of the workgroup.
+/// launch must satisfy layers_bound() <= it). split = 2: each row's edges are shared by two halves of the workgroup
+/// (block_threads a multiple of 128: a half is whole waves).
+/// d_tbs / d_tb_crc_ok (fused launches, optional): every codeblock of the launch is the only one of its transport
+/// block; the decoder then does the TB stage's work itself (pusch_tb.hip with one codeblock): a codeblock whose CRC
+/// passes also writes the first dm_desc::tb_bytes bytes of its message to d_tbs + tb_offset and sets
+/// d_tb_crc_ok[tb_index]; one that fails clears the flag and leaves the TB bytes alone.
 void launch_ldpc_decode_pk(int             bg,
                            int             mode,
                            int             max_layers,
@@ -256,7 +264,9 @@ void launch_ldpc_decode_pk(int             bg,
                            const dm_desc*  d_dm,
                            int8_t*         d_harq,
                            hipStream_t     stream,
-                           int8_t* const*  d_harq_cbs = nullptr);
+                           int8_t* const*  d_harq_cbs  = nullptr,
+                           uint8_t*        d_tbs       = nullptr,
+                           uint8_t*        d_tb_crc_ok = nullptr);
 
 /// Launches the two-codeblock packed decoder (ldpc_decode_pairs_kernel): workgroup w decodes d_desc[2 w + i] (slots
 /// with nof_llr = 0 are empty; the two slots share Z, scaling, iteration limit and CRC mode), codeblock slot i on lanes

@@ -518,8 +518,9 @@ OPTION_DECODER_PAIRS = 2          # 0 (default) / 1: Z = 144..192 codeblocks two
 OPTION_DECODER_FUSED_DEMATCH = 3  # 1 (default) / 0: every codeblock through the separate rate dematcher
 OPTION_ENCODER_BYTE_KERNEL = 4    # 0 (default) / 1: the byte-per-bit encoder kernel for every codeblock
 OPTION_ENCODER_ZERO_OUTPUT = 5    # 0 (default) / 1: the encoder always clears its output first
+OPTION_DECODER_TB_FOLD = 6        # 1 (default) / 0: single-codeblock TBs always through the separate TB stage
 OPTION_DEFAULTS = {OPTION_DECODER_SPLIT: -1, OPTION_DECODER_PAIRS: 0, OPTION_DECODER_FUSED_DEMATCH: 1,
-                   OPTION_ENCODER_BYTE_KERNEL: 0, OPTION_ENCODER_ZERO_OUTPUT: 0}
+                   OPTION_ENCODER_BYTE_KERNEL: 0, OPTION_ENCODER_ZERO_OUTPUT: 0, OPTION_DECODER_TB_FOLD: 1}
 
 
 class Context:

@@ -103,30 +103,16 @@ struct srsgpu_pusch_decoder_plan {
   uint32_t*             d_tb_acc   = nullptr;  ///< Per-TB CRC sums and slice counters (zero between executes).
   int                   nof_slices = 0;
   /// Every TB has one codeblock and every codeblock runs in a fused one-codeblock decoder launch: the decoder writes the
-  /// TBs and their flags (launch_ldpc_decode_pk d_tbs) and execute launches no TB stage
+  /// TBs and their flags (dec_launch_args::d_tbs) and execute launches no TB stage
   /// (SRSGPU_OPTION_DECODER_TB_FOLD).
   bool                  fold_tb    = false;
 };
 
 struct srsgpu_ldpc_decoder_plan {
   std::vector<crc_key> crc_refs;  ///< CRC tables referenced (top-level plans only).
-  /// One kernel launch per (base graph, kernel, layer bound): even lifting sizes go to the packed two-rows-per-lane
-  /// kernel (64 * ceil(Z / 128) lanes) built for at most max_layers layers, odd ones to the one-row-per-lane kernel
-  /// (64 * ceil(Z / 64) lanes).
-  struct group {
-    int       bg      = 1;
-    bool      packed  = false;
-    int       max_layers = 0;
-    int       split   = 1;   ///< 2: edge-split kernel (each row's edges over two wave halves), see upload_decoder_plan
-    int       pack    = 1;   ///< 2: two-codeblock workgroups (count = workgroups), see pair_layout_for
-    int       threads = 64;
-    int       count   = 0;
-    dec_desc* d_desc  = nullptr;
-    dm_desc*  d_dm    = nullptr;  ///< Fused rate dematching (DEC_FLAG_FUSED_DM): one dm_desc per codeblock, in order.
-  };
   srsgpu_context*    ctx  = nullptr;
   int                impl = SRSGPU_LDPC_IMPL_SIMD;
-  std::vector<group> groups;
+  std::vector<dec_group> groups;  ///< One kernel launch per (base graph, kernel, layer bound).
   uint64_t           input_llrs = 0;  ///< LLR bytes the decoder moves per execute: dec_desc::nof_llr per codeblock,
                                       ///< E + N for fused ones (codeword LLRs read, HARQ buffer written).
 };
@@ -739,6 +725,24 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
   auto upload = [&](void** dst, const void* src, size_t bytes) {
     return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
+  // Uploads a group's descriptors (dms: one per descriptor when fused, else empty; a descriptor with nof_llr = 0 is an
+  // empty slot of a two-codeblock workgroup) and adds it to the plan. The plan owns the group even when this fails.
+  auto add_group = [&](dec_group g, const std::vector<dec_desc>& descs, const std::vector<dm_desc>& dms) {
+    for (size_t k = 0; k < descs.size(); ++k) {
+      if (descs[k].nof_llr != 0u) {
+        // A fused codeblock reads its E codeword LLRs and writes the N-byte HARQ buffer instead.
+        plan->input_llrs += dms.empty() ? descs[k].nof_llr : static_cast<uint64_t>(dms[k].E) + dms[k].N;
+      }
+    }
+    const bool ok = upload(reinterpret_cast<void**>(&g.d_desc), descs.data(), descs.size() * sizeof(dec_desc)) &&
+                    (dms.empty() || upload(reinterpret_cast<void**>(&g.d_dm), dms.data(), dms.size() * sizeof(dm_desc)));
+    plan->groups.push_back(g);
+    return ok;
+  };
+  auto upload_failed = [&]() {
+    srsgpu_ldpc_decoder_plan_destroy(plan);
+    return fail(SRSGPU_ERR_HIP, "failed to upload decoder descriptors");
+  };
   for (const auto& kv : batch.groups) {
     const bool            fused = std::get<3>(kv.first);
     std::vector<dec_desc> cbs   = kv.second;
@@ -748,32 +752,22 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
       std::vector<dm_desc>  pair_dms;
       pair_layout_for(ctx, cbs, dms, fused, pairs, pair_dms);
       if (!pairs.empty()) {
-        srsgpu_ldpc_decoder_plan::group gp;
+        dec_group gp;
         gp.bg         = std::get<0>(kv.first);
         gp.packed     = true;
         gp.max_layers = std::get<2>(kv.first);
         gp.pack       = 2;
         gp.threads    = 192;
         gp.count      = static_cast<int>(pairs.size() / 2);
-        for (size_t k = 0; k < pairs.size(); ++k) {
-          if (pairs[k].nof_llr != 0u) {
-            plan->input_llrs += fused ? static_cast<uint64_t>(pair_dms[k].E) + pair_dms[k].N : pairs[k].nof_llr;
-          }
-        }
-        const bool ok = upload(reinterpret_cast<void**>(&gp.d_desc), pairs.data(), pairs.size() * sizeof(dec_desc)) &&
-                        (!fused || upload(reinterpret_cast<void**>(&gp.d_dm), pair_dms.data(),
-                                          pair_dms.size() * sizeof(dm_desc)));
-        plan->groups.push_back(gp);
-        if (!ok) {
-          srsgpu_ldpc_decoder_plan_destroy(plan);
-          return fail(SRSGPU_ERR_HIP, "failed to upload decoder descriptors");
+        if (!add_group(gp, pairs, pair_dms)) {
+          return upload_failed();
         }
       }
     }
     if (cbs.empty()) {
       continue;
     }
-    srsgpu_ldpc_decoder_plan::group g;
+    dec_group g;
     g.bg               = std::get<0>(kv.first);
     g.packed           = std::get<1>(kv.first);
     g.max_layers       = std::get<2>(kv.first);
@@ -791,81 +785,39 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
         g.threads *= 2;
       }
     }
-    if (!fused) {
-      for (const dec_desc& d : cbs) {
-        plan->input_llrs += d.nof_llr;
-      }
-    } else {
-      // A fused codeblock reads its E codeword LLRs and writes the N-byte HARQ buffer instead.
-      for (const dm_desc& m : dms) {
-        plan->input_llrs += static_cast<uint64_t>(m.E) + m.N;
-      }
-      const size_t dm_bytes = dms.size() * sizeof(dm_desc);
-      if (hipMalloc(&g.d_dm, dm_bytes) != hipSuccess ||
-          hipMemcpy(g.d_dm, dms.data(), dm_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        plan->groups.push_back(g);
-        srsgpu_ldpc_decoder_plan_destroy(plan);
-        return fail(SRSGPU_ERR_HIP, "failed to upload fused rate dematcher descriptors");
-      }
+    if (!add_group(g, cbs, dms)) {
+      return upload_failed();
     }
-    const dec_desc* src   = cbs.data();
-    const size_t    bytes = cbs.size() * sizeof(dec_desc);
-    if (hipMalloc(&g.d_desc, bytes) != hipSuccess ||
-        hipMemcpy(g.d_desc, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      plan->groups.push_back(g);
-      srsgpu_ldpc_decoder_plan_destroy(plan);
-      return fail(SRSGPU_ERR_HIP, "failed to upload decoder descriptors");
-    }
-    plan->groups.push_back(g);
   }
   *plan_out = plan;
   return SRSGPU_OK;
 }
 
-/// d_cw_llrs / d_harq: the codeword LLRs and the HARQ buffer of the fused groups (PUSCH plans; null otherwise).
-/// d_harq_cbs (PUSCH plans, optional): codeblock c's HARQ soft buffer is d_harq_cbs[c] (then d_llrs / d_harq unused).
-int execute_decoder_plan(const srsgpu_ldpc_decoder_plan* plan,
-                         const int8_t*                   d_llrs,
-                         uint8_t*                        d_out,
-                         int32_t*                        d_nof_iterations,
-                         uint8_t*                        d_cb_crc_ok,
-                         hipStream_t                     s,
-                         const int8_t*                   d_cw_llrs  = nullptr,
-                         int8_t*                         d_harq     = nullptr,
-                         int8_t* const*                  d_harq_cbs = nullptr,
-                         uint8_t*                        d_tbs      = nullptr,  // TB fold (srsgpu_pusch_decoder_plan::fold_tb:
-                                                                                // every group a fused one-codeblock launch)
-                         uint8_t*                        d_tb_crc_ok = nullptr)
+/// Launches the plan's groups with the buffers of one execution (a.mode and a.d_crc_tables come from the plan).
+int execute_decoder_plan(const srsgpu_ldpc_decoder_plan* plan, dec_launch_args a)
 {
+  a.mode         = plan->impl;
+  a.d_crc_tables = plan->ctx->d_crc_arena;
   for (const auto& g : plan->groups) {
+    if (g.d_dm != nullptr && (a.d_cw_llrs == nullptr || (a.d_harq == nullptr && a.d_harq_cbs == nullptr))) {
+      return fail(SRSGPU_ERR_INVALID_ARG, "fused decoder group without codeword LLRs / HARQ buffer");
+    }
     if (g.pack == 2) {
-      if (g.d_dm != nullptr && (d_cw_llrs == nullptr || (d_harq == nullptr && d_harq_cbs == nullptr))) {
-        return fail(SRSGPU_ERR_INVALID_ARG, "fused decoder group without codeword LLRs / HARQ buffer");
-      }
-      launch_ldpc_decode_pairs(g.bg, plan->impl, g.max_layers, g.d_desc, g.count, g.threads,
-                               g.d_dm != nullptr ? d_cw_llrs : d_llrs, d_out, d_nof_iterations,
-                               plan->ctx->d_pair_ab2[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, s, d_harq_cbs,
-                               g.d_dm, g.d_dm != nullptr ? d_harq : nullptr);
+      launch_ldpc_decode_pairs(g, plan->ctx->d_pair_ab2[g.bg - 1], a);
     } else if (g.packed) {
       // The edge-split kernel's CRC check takes a half's columns from its first lane: a half must be whole waves.
       if (g.split == 2 && g.threads % 128 != 0) {
         return fail(SRSGPU_ERR_INVALID_ARG, "edge-split decoder group of %d threads (not a multiple of 128)", g.threads);
       }
-      if (g.d_dm != nullptr && (d_cw_llrs == nullptr || (d_harq == nullptr && d_harq_cbs == nullptr))) {
-        return fail(SRSGPU_ERR_INVALID_ARG, "fused decoder group without codeword LLRs / HARQ buffer");
-      }
-      launch_ldpc_decode_pk(g.bg, plan->impl, g.max_layers, g.split, g.d_desc, g.count, g.threads,
-                            g.d_dm != nullptr ? d_cw_llrs : d_llrs, d_out, d_nof_iterations,
-                            plan->ctx->d_pair_ab[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, g.d_dm,
-                            g.d_dm != nullptr ? d_harq : nullptr, s, d_harq_cbs, d_tbs, d_tb_crc_ok);
+      launch_ldpc_decode_pk(g, plan->ctx->d_pair_ab[g.bg - 1], a);
     } else {
-      launch_ldpc_decode(g.bg, plan->impl, g.d_desc, g.count, g.threads, d_llrs, d_out, d_nof_iterations,
-                         plan->ctx->d_shifts32[g.bg - 1], plan->ctx->d_crc_arena, d_cb_crc_ok, s, d_harq_cbs);
+      launch_ldpc_decode(g, plan->ctx->d_shifts32[g.bg - 1], a);
     }
     HIP_TRY(hipGetLastError());
   }
   return SRSGPU_OK;
 }
+
 
 struct pusch_cb_params {
   int      bg, rv, qm, crc_poly, Z, filler, nof_crc_bits, max_iter;
@@ -998,7 +950,15 @@ int execute_pusch_cb_plan(const srsgpu_pusch_cb_plan* plan,
 {
   launch_rate_dematch(plan->impl, plan->d_dm, plan->nof_cbs, d_llrs, d_harq, d_cb_crc_ok, s);
   HIP_TRY(hipGetLastError());
-  return execute_decoder_plan(plan->dec, d_harq, d_out, d_nof_iterations, d_cb_crc_ok, s, d_llrs, d_harq);
+  dec_launch_args a;
+  a.d_llrs      = d_harq;
+  a.d_cw_llrs   = d_llrs;
+  a.d_out       = d_out;
+  a.d_results   = d_nof_iterations;
+  a.d_cb_crc_ok = d_cb_crc_ok;
+  a.d_harq      = d_harq;
+  a.stream      = s;
+  return execute_decoder_plan(plan->dec, a);
 }
 
 } // namespace
@@ -1047,7 +1007,12 @@ int srsgpu_ldpc_decoder_plan_execute(const srsgpu_ldpc_decoder_plan* plan,
   if (plan == nullptr || d_llrs == nullptr || d_out == nullptr || d_nof_iterations == nullptr) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
-  return execute_decoder_plan(plan, d_llrs, d_out, d_nof_iterations, nullptr, static_cast<hipStream_t>(stream));
+  dec_launch_args a;
+  a.d_llrs    = d_llrs;
+  a.d_out     = d_out;
+  a.d_results = d_nof_iterations;
+  a.stream    = static_cast<hipStream_t>(stream);
+  return execute_decoder_plan(plan, a);
 }
 
 void srsgpu_ldpc_decoder_plan_destroy(srsgpu_ldpc_decoder_plan* plan)
@@ -1513,7 +1478,7 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
   const auto& groups = plan->cbs->dec->groups;
   plan->fold_tb      = ctx->opt_decoder_tb_fold != 0 && nof_tbs > 0 && dms.empty() &&
                   std::all_of(tbs.begin(), tbs.end(), [](const tb_dec_desc& t) { return t.nof_cbs == 1; }) &&
-                  std::all_of(groups.begin(), groups.end(), [](const srsgpu_ldpc_decoder_plan::group& g) {
+                  std::all_of(groups.begin(), groups.end(), [](const dec_group& g) {
                     return g.packed && g.pack == 1 && g.d_dm != nullptr;
                   });
   if (nof_tbs > 0 && (hipMalloc(&plan->d_tb, tbs.size() * sizeof(tb_dec_desc)) != hipSuccess ||
@@ -1583,8 +1548,19 @@ int execute_pusch_decoder_plan(const srsgpu_pusch_decoder_plan* plan,
   HIP_TRY(hipGetLastError());
   stage_timer::mark(ev, 1, s);
   stage_timer::mark(evd, 0, s);
-  int r = execute_decoder_plan(plan->cbs->dec, d_harq, d_cb_msgs, d_cb_nof_iterations, d_cb_crc_ok, s, d_llrs, d_harq,
-                               d_harq_cbs, plan->fold_tb ? d_tbs : nullptr, plan->fold_tb ? d_tb_crc_ok : nullptr);
+  dec_launch_args a;
+  a.d_llrs      = d_harq;
+  a.d_cw_llrs   = d_llrs;
+  a.d_out       = d_cb_msgs;
+  a.d_results   = d_cb_nof_iterations;
+  a.d_cb_crc_ok = d_cb_crc_ok;
+  a.d_harq      = d_harq;
+  a.d_harq_cbs  = d_harq_cbs;
+  // TB fold: every group is a fused one-codeblock launch that writes the TBs and their flags itself.
+  a.d_tbs       = plan->fold_tb ? d_tbs : nullptr;
+  a.d_tb_crc_ok = plan->fold_tb ? d_tb_crc_ok : nullptr;
+  a.stream      = s;
+  int r         = execute_decoder_plan(plan->cbs->dec, a);
   if (r != SRSGPU_OK) {
     return r;
   }

@@ -437,37 +437,20 @@ int debug_read_decoder_profile(uint64_t* dst, size_t n)
 }
 #endif
 
-void launch_ldpc_decode(int             bg,
-                        int             mode,
-                        const dec_desc* d_desc,
-                        int             nof_cbs,
-                        int             block_threads,
-                        const int8_t*   d_llrs,
-                        uint8_t*        d_out,
-                        int32_t*        d_results,
-                        const uint32_t* d_shifts,
-                        const uint32_t* d_crc_tables,
-                        uint8_t*        d_cb_crc_ok,
-                        hipStream_t     stream,
-                        int8_t* const*  d_llr_cbs)
+void launch_ldpc_decode(const dec_group& g, const uint32_t* d_shifts, const dec_launch_args& a)
 {
-  if (nof_cbs <= 0) {
+  if (g.count <= 0) {
     return;
   }
-  const size_t lds = 0;
-  dim3         grid(nof_cbs), block(block_threads);
-  if (bg == 1) {
-    if (mode == 1) {
-      ldpc_decode_kernel<1, 1><<<grid, block, lds, stream>>>(d_desc, d_llrs, d_out, d_results, d_shifts, d_crc_tables, d_cb_crc_ok, d_llr_cbs);
-    } else {
-      ldpc_decode_kernel<1, 0><<<grid, block, lds, stream>>>(d_desc, d_llrs, d_out, d_results, d_shifts, d_crc_tables, d_cb_crc_ok, d_llr_cbs);
-    }
+  dim3 grid(g.count), block(g.threads);
+  auto launch = [&](auto kernel) {
+    kernel<<<grid, block, 0, a.stream>>>(g.d_desc, a.d_llrs, a.d_out, a.d_results, d_shifts, a.d_crc_tables,
+                                         a.d_cb_crc_ok, a.d_harq_cbs);
+  };
+  if (g.bg == 1) {
+    a.mode == 1 ? launch(ldpc_decode_kernel<1, 1>) : launch(ldpc_decode_kernel<1, 0>);
   } else {
-    if (mode == 1) {
-      ldpc_decode_kernel<2, 1><<<grid, block, lds, stream>>>(d_desc, d_llrs, d_out, d_results, d_shifts, d_crc_tables, d_cb_crc_ok, d_llr_cbs);
-    } else {
-      ldpc_decode_kernel<2, 0><<<grid, block, lds, stream>>>(d_desc, d_llrs, d_out, d_results, d_shifts, d_crc_tables, d_cb_crc_ok, d_llr_cbs);
-    }
+    a.mode == 1 ? launch(ldpc_decode_kernel<2, 1>) : launch(ldpc_decode_kernel<2, 0>);
   }
 }
 

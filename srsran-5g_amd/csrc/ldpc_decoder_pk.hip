@@ -433,16 +433,21 @@ __device__ __forceinline__ void pass2_half(int8_t* __restrict__ soft,
   sgw  = nsg;
 }
 
-/// LDS byte offset of position l (0 <= l < Z) inside a column.
-__device__ __forceinline__ uint32_t pair_pos(uint32_t l, uint32_t H)
-{
-  return (l < H) ? 2u * l : 2u * (l - H) + 1u;
-}
-
-/// Byte offset of position l (0 <= l < Z) of slot i within a column of an image that interleaves the pairs of PKN
-/// codeblocks (the two-codeblock workgroups below; PKN = 1, i = 0 is pair_pos).
+/// Geometry of a workgroup that decodes PKN codeblocks of one lifting size (PKN = 1: the one-codeblock kernel; PKN = 2:
+/// two codeblocks of Z <= 192 fill three waves, see ldpc_decode_pairs_kernel). The soft-bit images of the PKN slots
+/// are interleaved pair by pair.
 template <int PKN>
-__device__ __forceinline__ uint32_t pair_pos_pkn(uint32_t l, uint32_t H, uint32_t i)
+struct pk_geom {
+  static constexpr int CS           = PKN * SOFT_COL_STRIDE;   ///< column stride of the interleaved image
+  static constexpr int WAVES        = PKN * 192 / WAVE;        ///< most waves of a workgroup (Z = 384 slots)
+  static constexpr int RED          = 2 * PKN * WAVES * 2;     ///< CRC reduction ints: [parity][slot][wave][acc, zero]
+  static constexpr int SCRATCH_INTS = WAVES + RED + 2 * PKN;
+};
+
+/// LDS byte offset of position l (0 <= l < Z) of slot i within a column of the image of PKN codeblocks (PKN = 1,
+/// i = 0: 2 l below the half boundary, 2 (l - H) + 1 above it).
+template <int PKN>
+__device__ __forceinline__ uint32_t pair_pos(uint32_t l, uint32_t H, uint32_t i)
 {
   return ((l < H) ? 2u * PKN * l : 2u * PKN * (l - H) + 1u) + 2u * i;
 }
@@ -475,7 +480,7 @@ __device__ __forceinline__ void soft_put_x4(int8_t* __restrict__ soft,
 {
   const uint32_t cq  = __umulhi(k, magic);
   const uint32_t l   = k - __umul24(cq, Z);
-  int8_t*        dst = soft + __umul24(cq + 2u, PKN * SOFT_COL_STRIDE) + pair_pos_pkn<PKN>(l, H, slot);
+  int8_t*        dst = soft + __umul24(cq + 2u, PKN * SOFT_COL_STRIDE) + pair_pos<PKN>(l, H, slot);
   const uint32_t c   = clamp64_x4(w);
   dst[0]             = static_cast<int8_t>(c);
   dst[2 * PKN]       = static_cast<int8_t>(c >> 8);
@@ -504,7 +509,7 @@ __device__ __forceinline__ uint32_t hard_byte(const int8_t* __restrict__ soft,
 #pragma unroll
   for (uint32_t k = 0; k < 8; ++k) {
     if (i0 + k < nbits) {
-      byte |= static_cast<uint32_t>(cp[pair_pos_pkn<PKN>(l, H, slot)] <= 0) << (7u - k);
+      byte |= static_cast<uint32_t>(cp[pair_pos<PKN>(l, H, slot)] <= 0) << (7u - k);
     }
     ++l;
     if (l == Z) {
@@ -564,13 +569,257 @@ __device__ __forceinline__ void write_hard_bits_pk(const int8_t* __restrict__ so
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Front end of both packed kernels: one codeblock's soft bits into slot `slot` of the image of PKN codeblocks (the
+// one-codeblock kernel: PKN = 1, slot 0), either from its HARQ soft buffer (load_llrs) or, for a first transmission,
+// from the codeword LLRs with the rate dematching done on the way (load_dematched). Every thread of the workgroup
+// takes part; each returns the index of the last non-zero LLR it saw (ldpc_decoder_impl.cpp:94), -1 if none.
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// LLRs -> soft-bit image (ldpc_decoder_impl.cpp:152), as ldpc_decoder.hip but with the pair layout: a 16-byte vector
+/// inside one half of one column is a stride-2 PKN run of bytes. Decoder input clamp: +/-64 in the whole lifted columns
+/// of the input, the reference's LLR range (+/-infinity kept) in a trailing partial column. The punctured columns and
+/// every position beyond the input are zeroed.
+template <int NCOL, int PKN>
+__device__ __forceinline__ int load_llrs(int8_t* __restrict__ soft, const int8_t* __restrict__ llr, const dec_desc& d,
+                                         uint32_t slot)
+{
+  constexpr int  CS    = pk_geom<PKN>::CS;
+  const int      Z     = d.Z;
+  const uint32_t H     = static_cast<uint32_t>(Z) / 2u;
+  const int      n_llr = static_cast<int>(d.nof_llr);
+  const uint32_t ncols = __umulhi(static_cast<uint32_t>(n_llr), d.div_magic);
+  const uint32_t full  = ncols * static_cast<uint32_t>(Z);
+  int            last  = -1;
+  const uint32_t head  = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(llr)) & 15u;
+  const uint4*   vecs  = reinterpret_cast<const uint4*>(llr - head);
+  const int      nvec  = static_cast<int>((head + static_cast<uint32_t>(n_llr) + 15u) >> 4);
+  // 16-B vectors per lane in flight: the whole input span of the layer bound at Z = 384 with 192 lanes.
+  constexpr int  BATCH = ((NCOL - 2) * 384 / 16 + 191) / 192;
+  int            last_w = -1;
+  uint4          last_v = make_uint4(0u, 0u, 0u, 0u);
+  for (int w0 = threadIdx.x; w0 < nvec; w0 += BATCH * blockDim.x) {
+    uint4 val[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int w = w0 + j * blockDim.x;
+      val[j]      = (w < nvec) ? vecs[w] : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int w = w0 + j * blockDim.x;
+      if (w >= nvec) {
+        continue;
+      }
+      const uint32_t i0 = static_cast<uint32_t>(16 * w) - head;
+      const uint32_t c0 = __umulhi(i0, d.div_magic);
+      const uint32_t l0 = i0 - c0 * static_cast<uint32_t>(Z);
+      // Short path: the 16 LLRs lie in one column (every vector but the unaligned head and the input's tail).
+      // Consecutive positions are 2 PKN bytes apart. A vector may straddle the column's half boundary H: byte
+      // k >= H - l0 goes to 2 PKN (l - H) + 1 instead of 2 PKN l, i.e. its address moves by 1 - 2 PKN H (one
+      // bit-extract and one 24-bit multiply-add per byte, no branch), so a wave's straddling lane does not drag the
+      // whole wave through the per-byte general path.
+      const bool short_path = (16u * static_cast<uint32_t>(w) >= head) && (i0 + 16u <= full) &&
+                              (l0 + 16u <= static_cast<uint32_t>(Z));
+      if (short_path) {
+        int8_t*        dst   = soft + (c0 + 2) * CS + pair_pos<PKN>(l0, H, slot);
+        const uint32_t cross = (l0 < H && l0 + 16u > H) ? (0xffffu << (H - l0)) : 0u;  // bit k: byte k moves
+        const int      adj   = 1 - 2 * PKN * static_cast<int>(H);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int kk = 4 * q + k;
+            const int mv = static_cast<int>((cross >> kk) & 1u) * adj;
+            dst[2 * PKN * kk + mv] = static_cast<int8_t>(clamp_i(static_cast<int8_t>(word >> (8 * k)), -64, 64));
+          }
+        }
+        if ((val[j].x | val[j].y | val[j].z | val[j].w) != 0u) {
+          last_w = w;
+          last_v = val[j];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const uint32_t i = i0 + static_cast<uint32_t>(4 * q + k);
+            if (i < static_cast<uint32_t>(n_llr)) {
+              int v = static_cast<int8_t>(word >> (8 * k));
+              last  = (v != 0) ? static_cast<int>(i) : last;
+              v     = (i < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
+              const uint32_t cq = __umulhi(i, d.div_magic);
+              soft[(cq + 2) * CS + pair_pos<PKN>(i - cq * static_cast<uint32_t>(Z), H, slot)] = static_cast<int8_t>(v);
+            }
+          }
+        }
+      }
+    }
+  }
+  // Trailing-zero trim of the short path: the highest non-zero byte of the thread's last non-zero vector.
+  if (last_w >= 0) {
+    const uint32_t words[4] = {last_v.x, last_v.y, last_v.z, last_v.w};
+    int            hb       = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      hb = (words[q] != 0u) ? 4 * q + (31 - __clz(static_cast<int>(words[q]))) / 8 : hb;
+    }
+    const int i = 16 * last_w - static_cast<int>(head) + hb;
+    last        = i > last ? i : last;
+  }
+  // Punctured columns 0, 1 and every position beyond the input: threads [0, H) take position pair z. In the edge-split
+  // one-codeblock kernel these are the active lanes of half 0: a half is whole waves of at least H lanes.
+  const uint32_t z = threadIdx.x;
+  if (z < H) {
+    auto*          soft16 = reinterpret_cast<uint16_t*>(soft);
+    const uint32_t pz     = PKN * z + slot;  // 16-bit index of pair z within a column
+    soft16[(0 * CS) / 2 + pz] = 0;
+    soft16[(1 * CS) / 2 + pz] = 0;
+    int c = 2 + static_cast<int>(ncols);
+    if (static_cast<uint32_t>(n_llr) > full) {
+      const uint32_t rem = static_cast<uint32_t>(n_llr) - full;
+      if (z >= rem) {
+        soft[c * CS + 2 * pz] = 0;
+      }
+      if (z + H >= rem) {
+        soft[c * CS + 2 * pz + 1] = 0;
+      }
+      ++c;
+    }
+    for (; c < NCOL; ++c) {
+      soft16[(c * CS) / 2 + pz] = 0;
+    }
+  }
+  return last;
+}
+
+/// Fused rate dematching of a first transmission whose dematching is a plain copy (see FUSE below): the codeword LLRs
+/// llrs + dm.llr_offset go into the slot's image, which the caller has zeroed (punctured columns, positions beyond the
+/// input and the unreached tail), and into the HARQ soft buffer hb exactly as the separate rate_dematch_kernel would
+/// have written it (rate_dematcher.hip dematch_new_data: copies symbol-major, fillers +127, the unreached tail zeroed).
+template <int NCOL, int PKN>
+__device__ __forceinline__ int load_dematched(int8_t* __restrict__ soft, const int8_t* __restrict__ llrs,
+                                              const dec_desc& d, const dm_desc& dm, int8_t* __restrict__ hb,
+                                              uint32_t slot)
+{
+  constexpr int  CS    = pk_geom<PKN>::CS;
+  const int      Z     = d.Z;
+  const uint32_t H     = static_cast<uint32_t>(Z) / 2u;
+  const int      n_llr = static_cast<int>(d.nof_llr);
+  const uint32_t full  = __umulhi(static_cast<uint32_t>(n_llr), d.div_magic) * static_cast<uint32_t>(Z);
+  const int      E = static_cast<int>(dm.E), Qm = dm.Qm, R = E / Qm;
+  const int      Fl = dm.nof_filler, ninfo = static_cast<int>(dm.nsys) - Fl, Nh = static_cast<int>(dm.N);
+  const int8_t*  in   = llrs + dm.llr_offset;
+  int            last = -1;
+  // The decoder input clamp of load_llrs; trailing-zero trim over [0, n_llr).
+  auto soft_put = [&](int k, int v) {
+    if (static_cast<uint32_t>(k) < static_cast<uint32_t>(n_llr)) {
+      last              = (v != 0 && k > last) ? k : last;
+      const uint32_t cq = __umulhi(static_cast<uint32_t>(k), d.div_magic);
+      const int      cv = (static_cast<uint32_t>(k) < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
+      soft[(cq + 2) * CS + pair_pos<PKN>(static_cast<uint32_t>(k) - cq * static_cast<uint32_t>(Z), H, slot)] =
+          static_cast<int8_t>(cv);
+    }
+  };
+  auto put = [&](int k, int v) {
+    hb[k] = static_cast<int8_t>(v);
+    soft_put(k, v);
+  };
+  // Copies, symbol-major: lane r reads the Qm LLRs of symbol r and stores bit j at visit n = j R + r (position k =
+  // n, past the fillers once n >= ninfo); for a fixed j the lanes' HARQ stores are consecutive bytes. 256QAM with
+  // 4-aligned R, ninfo, fillers and HARQ buffer (every bench codeblock): a lane takes four consecutive symbols and
+  // writes each bit row's four HARQ bytes as one dword (8 dword stores per 4 symbols instead of 32 byte stores).
+  const bool q8   = Qm == 8 && ((dm.llr_offset & 7u) == 0u);
+  const bool q8x4 = q8 && ((R | ninfo | Fl | static_cast<int>(reinterpret_cast<uintptr_t>(hb))) & 3) == 0;
+  const bool z8   = (Z & 7) == 0;
+  if (q8x4) {
+    for (int r0 = 4 * static_cast<int>(threadIdx.x); r0 < R; r0 += 4 * static_cast<int>(blockDim.x)) {
+      uint2 v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        v[q] = *reinterpret_cast<const uint2*>(in + 8 * (r0 + q));
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t byte = (((j < 4) ? v[q].x : v[q].y) >> (8 * (j & 3))) & 0xffu;
+          w |= byte << (8 * q);
+        }
+        const int n = j * R + r0;  // n .. n + 3 on one side of ninfo (both multiples of 4)
+        const int k = n < ninfo ? n : n + Fl;  // a multiple of 4
+        *reinterpret_cast<uint32_t*>(hb + k) = w;
+        // The four positions as a group (soft_put_x4) when Z is a multiple of 8, per byte for other Z. The test
+        // against `full` is defensive: every plan the host builds gives a fused codeblock whole lifted columns
+        // (capi.cpp add_pusch_cb: n_llr a multiple of Z, E + F <= n_llr), so no group reaches a partial column.
+        if (z8 && static_cast<uint32_t>(k) + 4u <= full) {
+          soft_put_x4<PKN>(soft, w, static_cast<uint32_t>(k), static_cast<uint32_t>(Z), H, d.div_magic, slot, last);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
+          }
+        }
+      }
+    }
+  } else {
+    for (int r = threadIdx.x; r < R; r += blockDim.x) {
+      int8_t sym[8];
+      if (q8) {
+        // An 8-byte aligned 256QAM symbol is one load.
+        const uint2 v = *reinterpret_cast<const uint2*>(in + 8 * r);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          sym[j] = static_cast<int8_t>(((j < 4) ? v.x : v.y) >> (8 * (j & 3)));
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          sym[j] = (j < Qm) ? in[r * Qm + j] : 0;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < Qm) {
+          const int n = j * R + r;
+          put(n < ninfo ? n : n + Fl, sym[j]);
+        }
+      }
+    }
+  }
+  // Fillers: +infinity (ldpc_rate_dematcher_impl.cpp:172); then the unreached tail [E + F, N) zeroed (16-byte
+  // stores between the unaligned head and tail bytes).
+  for (int k = ninfo + static_cast<int>(threadIdx.x); k < ninfo + Fl; k += blockDim.x) {
+    put(k, 127);
+  }
+  {
+    const int t0 = E + Fl;
+    const int a0 = min(Nh, t0 + static_cast<int>((16u - (reinterpret_cast<uintptr_t>(hb + t0) & 15u)) & 15u));
+    const int nv = (Nh - a0) / 16;
+    const int a1 = a0 + 16 * nv;
+    if (static_cast<int>(threadIdx.x) < a0 - t0) {
+      hb[t0 + static_cast<int>(threadIdx.x)] = 0;
+    }
+    uint4* z16 = reinterpret_cast<uint4*>(hb + a0);
+    for (int q = threadIdx.x; q < nv; q += blockDim.x) {
+      z16[q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (static_cast<int>(threadIdx.x) < Nh - a1) {
+      hb[a1 + static_cast<int>(threadIdx.x)] = 0;
+    }
+  }
+  return last;
+}
+
 /// MAXL: compile-time bound on the number of layers (host-proven from the input length, dec_desc::nof_llr), so that
 /// only MAXL layers of check-to-variable state occupy VGPRs: the 4-layer high-rate codeblocks of a loaded cell run at
 /// twice the occupancy of the 46-layer worst case.
 /// FUSE: the codeblock is a first transmission whose rate dematching is a plain copy (rv 0, no limited buffer,
 /// ninfo <= E <= V: every systematic position is reached and nothing repeats): the kernel dematches the codeword LLRs
-/// itself (dms[blockIdx.x]) into the LDS image and writes the HARQ soft buffer the separate rate_dematch_kernel would
-/// have written (rate_dematcher.hip dematch_new_data: copies symbol-major, fillers +127, the unreached tail zeroed).
+/// itself (dms[blockIdx.x], load_dematched).
 template <int BG, int MODE, int MAXL, int SPLIT, bool FUSE>
 __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MAXL > 8 ? 4 : PK_MIN_WAVES_C2V)))) void ldpc_decode_pk_kernel(const dec_desc* __restrict__ descs,
                                                              const int8_t* __restrict__ llrs,
@@ -599,7 +848,7 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
   DEC_STAMP(0);
   DEC_PROF(29, __builtin_amdgcn_s_memrealtime());
   const dec_desc d = descs[blockIdx.x];
-  // Single-codeblock transport blocks written by the decoder (launch_ldpc_decode_pk d_tbs): fused launches only, whose
+  // Single-codeblock transport blocks written by the decoder (dec_launch_args::d_tbs): fused launches only, whose
   // codeblocks cannot take the already-decoded skip path below.
   const bool fold_tb = FUSE && tb_crc_ok != nullptr;
   if constexpr (FUSE) {
@@ -635,230 +884,22 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
   const int  nwaves = blockDim.x / WAVE;
   const int  lane   = threadIdx.x % WAVE;
 
-  // ---- LLRs -> soft-bit image (ldpc_decoder_impl.cpp:152), last non-zero LLR (:94); as ldpc_decoder.hip but with
-  // the pair layout: a 16-byte vector inside one half of one column is a stride-2 run of bytes. ----
-  // The codeblock's HARQ soft buffer (the input of an unfused codeblock, the output of a fused one): at its offset in
-  // the batch buffer, or wherever harq_cbs[cb] points (a persistent rx-buffer arena slot).
-  const int8_t*  llr   = (!FUSE && harq_cbs != nullptr) ? harq_cbs[d.cb_index] : llrs + d.llr_offset;
-  const int      n_llr = static_cast<int>(d.nof_llr);
-  const uint32_t ncols = __umulhi(static_cast<uint32_t>(n_llr), d.div_magic);
-  const uint32_t full  = ncols * static_cast<uint32_t>(Z);
-  int            last  = -1;
+  // ---- soft-bit image and last non-zero LLR: the shared front end with one slot ----
+  int last;
   if constexpr (FUSE) {
-    const dm_desc  dm    = dms[blockIdx.x];
-    const int      E     = static_cast<int>(dm.E), Qm = dm.Qm, R = E / Qm;
-    const int      Fl    = dm.nof_filler;
-    const int      ninfo = static_cast<int>(dm.nsys) - Fl;
-    const int      Nh    = static_cast<int>(dm.N);
-    const int8_t*  in    = llrs + dm.llr_offset;
-    int8_t*        hb    = (harq_cbs != nullptr) ? harq_cbs[d.cb_index] : harq + dm.harq_offset;
-    // The whole image starts at zero (punctured columns, positions beyond the input and the unreached tail).
-    {
-      uint4* s16 = reinterpret_cast<uint4*>(soft);
-      for (int q = threadIdx.x; q < NCOL * SOFT_COL_STRIDE / 16; q += blockDim.x) {
-        s16[q] = make_uint4(0u, 0u, 0u, 0u);
-      }
+    // The fused front end writes only its input positions: the whole image starts at zero.
+    uint4* s16 = reinterpret_cast<uint4*>(soft);
+    for (int q = threadIdx.x; q < NCOL * SOFT_COL_STRIDE / 16; q += blockDim.x) {
+      s16[q] = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
-    // Decoder input clamp (ldpc_decoder_impl.cpp:152): +/-64 in the whole lifted columns of the input, the
-    // reference's LLR range (+/-infinity kept) in a trailing partial column; trailing-zero trim over [0, n_llr).
-    auto soft_put = [&](int k, int v) {
-      if (static_cast<uint32_t>(k) < static_cast<uint32_t>(n_llr)) {
-        last              = (v != 0 && k > last) ? k : last;
-        const uint32_t cq = __umulhi(static_cast<uint32_t>(k), d.div_magic);
-        const int      cv = (static_cast<uint32_t>(k) < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
-        soft[(cq + 2) * SOFT_COL_STRIDE + pair_pos(static_cast<uint32_t>(k) - cq * static_cast<uint32_t>(Z), H)] =
-            static_cast<int8_t>(cv);
-      }
-    };
-    auto put = [&](int k, int v) {
-      hb[k] = static_cast<int8_t>(v);
-      soft_put(k, v);
-    };
-    // Copies, symbol-major: lane r reads the Qm LLRs of symbol r and stores bit j at visit n = j R + r (position k =
-    // n, past the fillers once n >= ninfo); for a fixed j the lanes' HARQ stores are consecutive bytes. 256QAM with
-    // 4-aligned R, ninfo, fillers and HARQ buffer (every bench codeblock): a lane takes four consecutive symbols and
-    // writes each bit row's four HARQ bytes as one dword (8 dword stores per 4 symbols instead of 32 byte stores).
-    const bool q8 = Qm == 8 && ((dm.llr_offset & 7u) == 0u);
-    const bool q8x4 = q8 &&
-                      ((R | ninfo | Fl | static_cast<int>(reinterpret_cast<uintptr_t>(hb))) & 3) == 0;
-    const bool z8 = (Z & 7) == 0;
-    if (q8x4) {
-      for (int r0 = 4 * static_cast<int>(threadIdx.x); r0 < R; r0 += 4 * static_cast<int>(blockDim.x)) {
-        uint2 v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          v[q] = *reinterpret_cast<const uint2*>(in + 8 * (r0 + q));
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          uint32_t w = 0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const uint32_t byte = (((j < 4) ? v[q].x : v[q].y) >> (8 * (j & 3))) & 0xffu;
-            w |= byte << (8 * q);
-          }
-          const int n = j * R + r0;  // n .. n + 3 on one side of ninfo (both multiples of 4)
-          const int k = n < ninfo ? n : n + Fl;  // a multiple of 4
-          *reinterpret_cast<uint32_t*>(hb + k) = w;
-          // The four positions as a group (soft_put_x4) when Z is a multiple of 8, per byte for other Z. The test
-          // against `full` is defensive: every plan the host builds gives a fused codeblock whole lifted columns
-          // (capi.cpp add_pusch_cb: n_llr a multiple of Z, E + F <= n_llr), so no group reaches a partial column.
-          if (z8 && static_cast<uint32_t>(k) + 4u <= full) {
-            soft_put_x4<1>(soft, w, static_cast<uint32_t>(k), static_cast<uint32_t>(Z), H, d.div_magic, 0u, last);
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
-            }
-          }
-        }
-      }
-    } else {
-      for (int r = threadIdx.x; r < R; r += blockDim.x) {
-        int8_t sym[8];
-        if (q8) {
-          const uint2 v = *reinterpret_cast<const uint2*>(in + 8 * r);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            sym[j] = static_cast<int8_t>(((j < 4) ? v.x : v.y) >> (8 * (j & 3)));
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            sym[j] = (j < Qm) ? in[r * Qm + j] : 0;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (j < Qm) {
-            const int n = j * R + r;
-            put(n < ninfo ? n : n + Fl, sym[j]);
-          }
-        }
-      }
-    }
-    // Fillers: +infinity (ldpc_rate_dematcher_impl.cpp:172); then the unreached tail [E + F, N) zeroed (16-byte
-    // stores between the unaligned head and tail bytes).
-    for (int k = ninfo + static_cast<int>(threadIdx.x); k < ninfo + Fl; k += blockDim.x) {
-      put(k, 127);
-    }
-    {
-      const int t0 = E + Fl;
-      const int a0 = min(Nh, t0 + static_cast<int>((16u - (reinterpret_cast<uintptr_t>(hb + t0) & 15u)) & 15u));
-      const int nv = (Nh - a0) / 16;
-      const int a1 = a0 + 16 * nv;
-      if (static_cast<int>(threadIdx.x) < a0 - t0) {
-        hb[t0 + static_cast<int>(threadIdx.x)] = 0;
-      }
-      uint4* z16 = reinterpret_cast<uint4*>(hb + a0);
-      for (int q = threadIdx.x; q < nv; q += blockDim.x) {
-        z16[q] = make_uint4(0u, 0u, 0u, 0u);
-      }
-      if (static_cast<int>(threadIdx.x) < Nh - a1) {
-        hb[a1 + static_cast<int>(threadIdx.x)] = 0;
-      }
-    }
+    // The codeblock's HARQ soft buffer (the output of a fused codeblock, the input of an unfused one): at its offset
+    // in the batch buffer, or wherever harq_cbs[cb] points (a persistent rx-buffer arena slot).
+    const dm_desc dm = dms[blockIdx.x];
+    int8_t*       hq = (harq_cbs != nullptr) ? harq_cbs[d.cb_index] : harq + dm.harq_offset;
+    last             = load_dematched<NCOL, 1>(soft, llrs, d, dm, hq, 0u);
   } else {
-    {
-      const uint32_t head   = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(llr)) & 15u;
-      const uint4*   vecs   = reinterpret_cast<const uint4*>(llr - head);
-      const int      nvec   = static_cast<int>((head + static_cast<uint32_t>(n_llr) + 15u) >> 4);
-      // 16-B vectors per lane in flight: the whole input span of the layer bound at Z = 384 with 192 lanes.
-      constexpr int  BATCH  = ((NCOL - 2) * 384 / 16 + 191) / 192;
-      int            last_w = -1;
-      uint4          last_v = make_uint4(0u, 0u, 0u, 0u);
-      for (int w0 = threadIdx.x; w0 < nvec; w0 += BATCH * blockDim.x) {
-        uint4 val[BATCH];
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) {
-          const int w = w0 + j * blockDim.x;
-          val[j]      = (w < nvec) ? vecs[w] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) {
-          const int w = w0 + j * blockDim.x;
-          if (w >= nvec) {
-            continue;
-          }
-          const uint32_t i0 = static_cast<uint32_t>(16 * w) - head;
-          const uint32_t c0 = __umulhi(i0, d.div_magic);
-          const uint32_t l0 = i0 - c0 * static_cast<uint32_t>(Z);
-          // Short path: the 16 LLRs lie in one column (every vector but the unaligned head and the input's tail). A
-          // vector may straddle the column's half boundary H: byte k >= H - l0 goes to 2 (l - H) + 1 instead of 2 l,
-          // i.e. its address moves by 1 - 2H (one bit-extract and one 24-bit multiply-add per byte, no branch), so a
-          // wave's straddling lane does not drag the whole wave through the per-byte general path.
-          const bool short_path = (16u * static_cast<uint32_t>(w) >= head) && (i0 + 16u <= full) &&
-                                  (l0 + 16u <= static_cast<uint32_t>(Z));
-          if (short_path) {
-            int8_t*        dst   = soft + (c0 + 2) * SOFT_COL_STRIDE + pair_pos(l0, H);
-            const uint32_t cross = (l0 < H && l0 + 16u > H) ? (0xffffu << (H - l0)) : 0u;  // bit k: byte k moves
-            const int      adj   = 1 - 2 * static_cast<int>(H);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
-#pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                const int kk  = 4 * q + k;
-                const int mv  = static_cast<int>((cross >> kk) & 1u) * adj;
-                dst[2 * kk + mv] = static_cast<int8_t>(clamp_i(static_cast<int8_t>(word >> (8 * k)), -64, 64));
-              }
-            }
-            if ((val[j].x | val[j].y | val[j].z | val[j].w) != 0u) {
-              last_w = w;
-              last_v = val[j];
-            }
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
-#pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                const uint32_t i = i0 + static_cast<uint32_t>(4 * q + k);
-                if (i < static_cast<uint32_t>(n_llr)) {
-                  int v = static_cast<int8_t>(word >> (8 * k));
-                  last  = (v != 0) ? static_cast<int>(i) : last;
-                  v     = (i < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
-                  const uint32_t cq = __umulhi(i, d.div_magic);
-                  soft[(cq + 2) * SOFT_COL_STRIDE + pair_pos(i - cq * static_cast<uint32_t>(Z), H)] =
-                      static_cast<int8_t>(v);
-                }
-              }
-            }
-          }
-        }
-      }
-      if (last_w >= 0) {
-        const uint32_t words[4] = {last_v.x, last_v.y, last_v.z, last_v.w};
-        int            hb       = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          hb = (words[q] != 0u) ? 4 * q + (31 - __clz(static_cast<int>(words[q]))) / 8 : hb;
-        }
-        const int i = 16 * last_w - static_cast<int>(head) + hb;
-        last        = i > last ? i : last;
-      }
-    }
-    // Zero the punctured columns 0, 1 and every position beyond the input.
-    if (active && half == 0) {
-      auto* soft16 = reinterpret_cast<uint16_t*>(soft);
-      soft16[(0 * SOFT_COL_STRIDE) / 2 + z] = 0;
-      soft16[(1 * SOFT_COL_STRIDE) / 2 + z] = 0;
-      int c = 2 + static_cast<int>(ncols);
-      if (static_cast<uint32_t>(n_llr) > full) {
-        const uint32_t rem = static_cast<uint32_t>(n_llr) - full;
-        if (static_cast<uint32_t>(z) >= rem) {
-          soft[c * SOFT_COL_STRIDE + 2 * z] = 0;
-        }
-        if (static_cast<uint32_t>(z) + H >= rem) {
-          soft[c * SOFT_COL_STRIDE + 2 * z + 1] = 0;
-        }
-        ++c;
-      }
-      for (; c < NCOL; ++c) {
-        soft16[(c * SOFT_COL_STRIDE) / 2 + z] = 0;
-      }
-    }
+    last = load_llrs<NCOL, 1>(soft, (harq_cbs != nullptr) ? harq_cbs[d.cb_index] : llrs + d.llr_offset, d, 0u);
   }
   last = wave_max(last);
   if (lane == 0) {
@@ -1100,131 +1141,13 @@ __global__ __launch_bounds__(192 * SPLIT, (SPLIT == 2 ? 2 : (MAXL > 16 ? 3 : (MA
 // packed kernel's address arithmetic (min(u + A, u + B) in 16-bit halves, partner byte a ^ 1) and its column
 // immediates are unchanged: row_update_pk runs as is, with column stride CS.
 //
-// Per codeblock as in the plain kernel: HARQ skip, LLR load, layer count, CRC early stop, hard decisions and results.
+// Per codeblock as in the plain kernel: HARQ skip, the shared front end (load_llrs / load_dematched with the slot's
+// addresses; FUSE: slot i's dm_desc is dms[PKN w + i]), layer count, CRC early stop, hard decisions and results.
 // The slots of a workgroup share the iteration loop (a stopped codeblock's lanes idle through the layers and barriers
 // until the other one stops). The host pairs codeblocks with the same Z, scaling, iteration limit and CRC mode
 // (descs[2 w + i], an empty slot has nof_llr = 0). Measured (profiles/r5_decoder_pk2_scaling.txt): 2-7 % faster at six
 // iterations, equal or slower under early stop - opt-in.
 // ---------------------------------------------------------------------------------------------------------------------
-/// Geometry of a PKN-codeblock workgroup (PKN = 2: two codeblocks of Z <= 192 fill three waves).
-template <int PKN>
-struct pk_geom {
-  static constexpr int CS           = PKN * SOFT_COL_STRIDE;   ///< column stride of the interleaved image
-  static constexpr int WAVES        = PKN * 192 / WAVE;        ///< most waves of a workgroup (Z = 384 slots)
-  static constexpr int RED          = 2 * PKN * WAVES * 2;     ///< CRC reduction ints: [parity][slot][wave][acc, zero]
-  static constexpr int SCRATCH_INTS = WAVES + RED + 2 * PKN;
-};
-
-/// LLRs of one codeblock -> its slot of the interleaved image (ldpc_decoder_impl.cpp:152; the plain kernel's load with
-/// the slot's addresses), the punctured columns and every position beyond the input zeroed. Returns this thread's
-/// index of the last non-zero LLR it saw (ldpc_decoder_impl.cpp:94), -1 if none.
-template <int NCOL, int PKN>
-__device__ __forceinline__ int load_llrs_pkn(int8_t* __restrict__ soft, const int8_t* __restrict__ llr,
-                                             const dec_desc& d, uint32_t slot)
-{
-  const int      Z     = d.Z;
-  const uint32_t H     = static_cast<uint32_t>(Z) / 2u;
-  const int      n_llr = static_cast<int>(d.nof_llr);
-  const uint32_t ncols = __umulhi(static_cast<uint32_t>(n_llr), d.div_magic);
-  const uint32_t full  = ncols * static_cast<uint32_t>(Z);
-  int            last  = -1;
-  const uint32_t head  = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(llr)) & 15u;
-  const uint4*   vecs  = reinterpret_cast<const uint4*>(llr - head);
-  const int      nvec  = static_cast<int>((head + static_cast<uint32_t>(n_llr) + 15u) >> 4);
-  constexpr int  BATCH = ((NCOL - 2) * 384 / 16 + 191) / 192;
-  int            last_w = -1;
-  uint4          last_v = make_uint4(0u, 0u, 0u, 0u);
-  for (int w0 = threadIdx.x; w0 < nvec; w0 += BATCH * blockDim.x) {
-    uint4 val[BATCH];
-#pragma unroll
-    for (int j = 0; j < BATCH; ++j) {
-      const int w = w0 + j * blockDim.x;
-      val[j]      = (w < nvec) ? vecs[w] : make_uint4(0u, 0u, 0u, 0u);
-    }
-#pragma unroll
-    for (int j = 0; j < BATCH; ++j) {
-      const int w = w0 + j * blockDim.x;
-      if (w >= nvec) {
-        continue;
-      }
-      const uint32_t i0 = static_cast<uint32_t>(16 * w) - head;
-      const uint32_t c0 = __umulhi(i0, d.div_magic);
-      const uint32_t l0 = i0 - c0 * static_cast<uint32_t>(Z);
-      const bool short_path = (16u * static_cast<uint32_t>(w) >= head) && (i0 + 16u <= full) &&
-                              (l0 + 16u <= static_cast<uint32_t>(Z));
-      if (short_path) {
-        // Consecutive positions are 2 PKN bytes apart; a byte past the half boundary moves by 1 - 2 PKN H.
-        int8_t*        dst   = soft + (c0 + 2) * pk_geom<PKN>::CS + pair_pos_pkn<PKN>(l0, H, slot);
-        const uint32_t cross = (l0 < H && l0 + 16u > H) ? (0xffffu << (H - l0)) : 0u;
-        const int      adj   = 1 - 2 * PKN * static_cast<int>(H);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int kk = 4 * q + k;
-            const int mv = static_cast<int>((cross >> kk) & 1u) * adj;
-            dst[2 * PKN * kk + mv] = static_cast<int8_t>(clamp_i(static_cast<int8_t>(word >> (8 * k)), -64, 64));
-          }
-        }
-        if ((val[j].x | val[j].y | val[j].z | val[j].w) != 0u) {
-          last_w = w;
-          last_v = val[j];
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t word = (q == 0) ? val[j].x : (q == 1) ? val[j].y : (q == 2) ? val[j].z : val[j].w;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const uint32_t i = i0 + static_cast<uint32_t>(4 * q + k);
-            if (i < static_cast<uint32_t>(n_llr)) {
-              int v = static_cast<int8_t>(word >> (8 * k));
-              last  = (v != 0) ? static_cast<int>(i) : last;
-              v     = (i < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
-              const uint32_t cq = __umulhi(i, d.div_magic);
-              soft[(cq + 2) * pk_geom<PKN>::CS + pair_pos_pkn<PKN>(i - cq * static_cast<uint32_t>(Z), H, slot)] = static_cast<int8_t>(v);
-            }
-          }
-        }
-      }
-    }
-  }
-  if (last_w >= 0) {
-    const uint32_t words[4] = {last_v.x, last_v.y, last_v.z, last_v.w};
-    int            hb       = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      hb = (words[q] != 0u) ? 4 * q + (31 - __clz(static_cast<int>(words[q]))) / 8 : hb;
-    }
-    const int i = 16 * last_w - static_cast<int>(head) + hb;
-    last        = i > last ? i : last;
-  }
-  // Punctured columns 0, 1 and every position beyond the input: threads [0, H) take position pair z.
-  const uint32_t z = threadIdx.x;
-  if (z < H) {
-    auto* soft16 = reinterpret_cast<uint16_t*>(soft);
-    const uint32_t pz = PKN * z + slot;  // 16-bit index of pair z within a column
-    soft16[(0 * pk_geom<PKN>::CS) / 2 + pz] = 0;
-    soft16[(1 * pk_geom<PKN>::CS) / 2 + pz] = 0;
-    int c = 2 + static_cast<int>(ncols);
-    if (static_cast<uint32_t>(n_llr) > full) {
-      const uint32_t rem = static_cast<uint32_t>(n_llr) - full;
-      if (z >= rem) {
-        soft[c * pk_geom<PKN>::CS + 2 * pz] = 0;
-      }
-      if (z + H >= rem) {
-        soft[c * pk_geom<PKN>::CS + 2 * pz + 1] = 0;
-      }
-      ++c;
-    }
-    for (; c < NCOL; ++c) {
-      soft16[(c * pk_geom<PKN>::CS) / 2 + pz] = 0;
-    }
-  }
-  return last;
-}
-
 /// Hard decisions of one slot's K*Z systematic bits, written by the slot's H lanes (lane z: bytes z, z + H, ...).
 template <int PKN>
 __device__ __forceinline__ void write_hard_bits_pkn(const int8_t* __restrict__ soft, uint8_t* __restrict__ out,
@@ -1238,108 +1161,6 @@ __device__ __forceinline__ void write_hard_bits_pkn(const int8_t* __restrict__ s
     out[b] = static_cast<uint8_t>(hard_byte<PKN>(soft, static_cast<uint32_t>(b), static_cast<uint32_t>(nbits),
                                                  static_cast<uint32_t>(Z), H, magic, slot));
   }
-}
-
-/// FUSE (as the one-codeblock kernel's): slot i's first transmission is dematched by the workgroup from the codeword
-/// LLRs (llrs + dms[PKN w + i].llr_offset) into its slot of the image and into its HARQ soft buffer (harq +
-/// harq_offset, or llr_cbs[cb]); the image is zeroed first. Returns this thread's last non-zero input position.
-template <int NCOL, int PKN>
-__device__ __forceinline__ int load_fused_pkn(int8_t* __restrict__ soft, const int8_t* __restrict__ llrs,
-                                              const dec_desc& d, const dm_desc& dm, int8_t* __restrict__ hb,
-                                              uint32_t slot)
-{
-  const int      Z     = d.Z;
-  const uint32_t H     = static_cast<uint32_t>(Z) / 2u;
-  const int      n_llr = static_cast<int>(d.nof_llr);
-  const uint32_t full  = __umulhi(static_cast<uint32_t>(n_llr), d.div_magic) * static_cast<uint32_t>(Z);
-  const int      E = static_cast<int>(dm.E), Qm = dm.Qm, R = E / Qm;
-  const int      Fl = dm.nof_filler, ninfo = static_cast<int>(dm.nsys) - Fl, Nh = static_cast<int>(dm.N);
-  const int8_t*  in   = llrs + dm.llr_offset;
-  int            last = -1;
-  // The one-codeblock kernel's soft_put / put (ldpc_decoder_impl.cpp:152 clamps, :94 trailing-zero trim) at the slot's
-  // interleaved addresses.
-  auto soft_put = [&](int k, int v) {
-    if (static_cast<uint32_t>(k) < static_cast<uint32_t>(n_llr)) {
-      last              = (v != 0 && k > last) ? k : last;
-      const uint32_t cq = __umulhi(static_cast<uint32_t>(k), d.div_magic);
-      const int      cv = (static_cast<uint32_t>(k) < full) ? clamp_i(v, -64, 64) : clamp_i(v, -SOFT_INF, SOFT_INF);
-      soft[(cq + 2) * pk_geom<PKN>::CS + pair_pos_pkn<PKN>(static_cast<uint32_t>(k) - cq * static_cast<uint32_t>(Z), H,
-                                                        slot)] = static_cast<int8_t>(cv);
-    }
-  };
-  auto put = [&](int k, int v) {
-    hb[k] = static_cast<int8_t>(v);
-    soft_put(k, v);
-  };
-  const bool q8   = Qm == 8 && ((dm.llr_offset & 7u) == 0u);
-  const bool q8x4 = q8 &&
-                    ((R | ninfo | Fl | static_cast<int>(reinterpret_cast<uintptr_t>(hb))) & 3) == 0;
-  const bool z8   = (Z & 7) == 0;
-  if (q8x4) {
-    for (int r0 = 4 * static_cast<int>(threadIdx.x); r0 < R; r0 += 4 * static_cast<int>(blockDim.x)) {
-      uint2 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        v[q] = *reinterpret_cast<const uint2*>(in + 8 * (r0 + q));
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          w |= ((((j < 4) ? v[q].x : v[q].y) >> (8 * (j & 3))) & 0xffu) << (8 * q);
-        }
-        const int n = j * R + r0;
-        const int k = n < ninfo ? n : n + Fl;
-        *reinterpret_cast<uint32_t*>(hb + k) = w;
-        // As the one-codeblock kernel: the group of four inside the whole lifted columns, else per byte.
-        if (z8 && static_cast<uint32_t>(k) + 4u <= full) {
-          soft_put_x4<PKN>(soft, w, static_cast<uint32_t>(k), static_cast<uint32_t>(Z), H, d.div_magic, slot, last);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            soft_put(k + q, static_cast<int8_t>(w >> (8 * q)));
-          }
-        }
-      }
-    }
-  } else {
-    for (int r = threadIdx.x; r < R; r += blockDim.x) {
-      int8_t sym[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        sym[j] = (j < Qm) ? in[r * Qm + j] : 0;
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (j < Qm) {
-          const int n = j * R + r;
-          put(n < ninfo ? n : n + Fl, sym[j]);
-        }
-      }
-    }
-  }
-  // Fillers: +infinity (ldpc_rate_dematcher_impl.cpp:172); the unreached tail [E + F, N) of the HARQ buffer zeroed.
-  for (int k = ninfo + static_cast<int>(threadIdx.x); k < ninfo + Fl; k += blockDim.x) {
-    put(k, 127);
-  }
-  {
-    const int t0 = E + Fl;  // 16-byte stores between the unaligned head and tail bytes
-    const int a0 = min(Nh, t0 + static_cast<int>((16u - (reinterpret_cast<uintptr_t>(hb + t0) & 15u)) & 15u));
-    const int nv = (Nh - a0) / 16;
-    const int a1 = a0 + 16 * nv;
-    if (static_cast<int>(threadIdx.x) < a0 - t0) {
-      hb[t0 + static_cast<int>(threadIdx.x)] = 0;
-    }
-    uint4* z16 = reinterpret_cast<uint4*>(hb + a0);
-    for (int q = threadIdx.x; q < nv; q += blockDim.x) {
-      z16[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (static_cast<int>(threadIdx.x) < Nh - a1) {
-      hb[a1 + static_cast<int>(threadIdx.x)] = 0;
-    }
-  }
-  return last;
 }
 
 template <int BG, int MODE, int MAXL, int PKN, bool FUSE>
@@ -1419,10 +1240,10 @@ __global__ __launch_bounds__(64 * pk_geom<PKN>::WAVES, (MAXL > 8 ? 4 : PK_MIN_BL
         }
         const dm_desc dm = dms[static_cast<size_t>(blockIdx.x) * PKN + i];
         int8_t*       hb = (llr_cbs != nullptr) ? llr_cbs[d.cb_index] : harq + dm.harq_offset;
-        last = load_fused_pkn<NCOL, PKN>(soft, llrs, d, dm, hb, static_cast<uint32_t>(i));
+        last = load_dematched<NCOL, PKN>(soft, llrs, d, dm, hb, static_cast<uint32_t>(i));
       } else {
-        last = load_llrs_pkn<NCOL, PKN>(soft, (llr_cbs != nullptr) ? llr_cbs[d.cb_index] : llrs + d.llr_offset, d,
-                                        static_cast<uint32_t>(i));
+        last = load_llrs<NCOL, PKN>(soft, (llr_cbs != nullptr) ? llr_cbs[d.cb_index] : llrs + d.llr_offset, d,
+                                    static_cast<uint32_t>(i));
       }
       last     = wave_max(last);
       if (lane == 0) {
@@ -1600,104 +1421,76 @@ int debug_read_decoder_profile_pk(uint64_t* dst, size_t n)
 }
 #endif
 
-void launch_ldpc_decode_pk(int             bg,
-                           int             mode,
-                           int             max_layers,
-                           int             split,
-                           const dec_desc* d_desc,
-                           int             nof_cbs,
-                           int             block_threads,
-                           const int8_t*   d_llrs,
-                           uint8_t*        d_out,
-                           int32_t*        d_results,
-                           const uint32_t* d_ab,
-                           const uint32_t* d_crc_tables,
-                           uint8_t*        d_cb_crc_ok,
-                           const dm_desc*  d_dm,
-                           int8_t*         d_harq,
-                           hipStream_t     stream,
-                           int8_t* const*  d_harq_cbs,
-                           uint8_t*        d_tbs,
-                           uint8_t*        d_tb_crc_ok)
+namespace {
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+/// Maps the run-time (bg, mode, max_layers) of a launch to compile-time constants: calls f(BG, MODE, MAXL) with
+/// integral constants, MAXL the layer class (8, 16, or all the base graph's layers where ALL_LAYERS says that class
+/// exists).
+template <bool ALL_LAYERS, typename F>
+void with_decoder_class(int bg, int mode, int max_layers, F&& f)
 {
-  if (nof_cbs <= 0) {
+  auto with_bg = [&](auto BG) {
+    auto with_mode = [&](auto MODE) {
+      if (max_layers <= 8) {
+        f(BG, MODE, int_c<8>{});
+      } else if (!ALL_LAYERS || max_layers <= 16) {
+        f(BG, MODE, int_c<16>{});
+      } else if constexpr (ALL_LAYERS) {
+        f(BG, MODE, int_c<bg_t<decltype(BG)::value>::M>{});
+      }
+    };
+    mode == 1 ? with_mode(int_c<1>{}) : with_mode(int_c<0>{});
+  };
+  bg == 1 ? with_bg(int_c<1>{}) : with_bg(int_c<2>{});
+}
+} // namespace
+
+void launch_ldpc_decode_pk(const dec_group& g, const uint32_t* d_ab, const dec_launch_args& a)
+{
+  if (g.count <= 0) {
     return;
   }
-  dim3 grid(nof_cbs), block(block_threads);
-  const bool fuse = d_dm != nullptr;
+  dim3 grid(g.count), block(g.threads);
   // The TB fold needs the dm_desc's TB fields: fused launches only.
-  uint8_t* tb_ok = (fuse && d_tbs != nullptr) ? d_tb_crc_ok : nullptr;
-#define SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, SPLIT_)                                                                   \
-  (fuse ? ldpc_decode_pk_kernel<BG_, MODE_, MAXL_, SPLIT_, true><<<grid, block, 0, stream>>>(                          \
-              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, d_dm, d_harq, d_harq_cbs, d_tbs,     \
-              tb_ok)                                                                                                   \
-        : ldpc_decode_pk_kernel<BG_, MODE_, MAXL_, SPLIT_, false><<<grid, block, 0, stream>>>(                         \
-              d_desc, d_llrs, d_out, d_results, d_ab, d_crc_tables, d_cb_crc_ok, nullptr, nullptr, d_harq_cbs,         \
-              nullptr, nullptr))
-#define SRSGPU_PK_LAUNCH(BG_, MODE_, MAXL_)                                                                            \
-  (split == 2 ? SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, 2) : SRSGPU_PK_LAUNCH1(BG_, MODE_, MAXL_, 1))
-  if (bg == 1) {
-    if (max_layers <= 8) {
-      mode == 1 ? SRSGPU_PK_LAUNCH(1, 1, 8) : SRSGPU_PK_LAUNCH(1, 0, 8);
-    } else if (max_layers <= 16) {
-      mode == 1 ? SRSGPU_PK_LAUNCH(1, 1, 16) : SRSGPU_PK_LAUNCH(1, 0, 16);
-    } else {
-      mode == 1 ? SRSGPU_PK_LAUNCH(1, 1, kBG1_M) : SRSGPU_PK_LAUNCH(1, 0, kBG1_M);
-    }
-  } else {
-    if (max_layers <= 8) {
-      mode == 1 ? SRSGPU_PK_LAUNCH(2, 1, 8) : SRSGPU_PK_LAUNCH(2, 0, 8);
-    } else if (max_layers <= 16) {
-      mode == 1 ? SRSGPU_PK_LAUNCH(2, 1, 16) : SRSGPU_PK_LAUNCH(2, 0, 16);
-    } else {
-      mode == 1 ? SRSGPU_PK_LAUNCH(2, 1, kBG2_M) : SRSGPU_PK_LAUNCH(2, 0, kBG2_M);
-    }
-  }
-#undef SRSGPU_PK_LAUNCH
-#undef SRSGPU_PK_LAUNCH1
+  uint8_t* tb_ok = (g.d_dm != nullptr && a.d_tbs != nullptr) ? a.d_tb_crc_ok : nullptr;
+  with_decoder_class<true>(g.bg, a.mode, g.max_layers, [&](auto BG, auto MODE, auto MAXL) {
+    auto with_split = [&](auto SPLIT) {
+      constexpr int bg = decltype(BG)::value, mode = decltype(MODE)::value, maxl = decltype(MAXL)::value;
+      constexpr int split = decltype(SPLIT)::value;
+      if (g.d_dm != nullptr) {
+        ldpc_decode_pk_kernel<bg, mode, maxl, split, true><<<grid, block, 0, a.stream>>>(
+            g.d_desc, a.d_cw_llrs, a.d_out, a.d_results, d_ab, a.d_crc_tables, a.d_cb_crc_ok, g.d_dm, a.d_harq,
+            a.d_harq_cbs, a.d_tbs, tb_ok);
+      } else {
+        ldpc_decode_pk_kernel<bg, mode, maxl, split, false><<<grid, block, 0, a.stream>>>(
+            g.d_desc, a.d_llrs, a.d_out, a.d_results, d_ab, a.d_crc_tables, a.d_cb_crc_ok, nullptr, nullptr,
+            a.d_harq_cbs, nullptr, nullptr);
+      }
+    };
+    g.split == 2 ? with_split(int_c<2>{}) : with_split(int_c<1>{});
+  });
 }
 
-void launch_ldpc_decode_pairs(int             bg,
-                              int             mode,
-                              int             max_layers,
-                              const dec_desc* d_desc,
-                              int             nof_groups,
-                              int             block_threads,
-                              const int8_t*   d_llrs,
-                              uint8_t*        d_out,
-                              int32_t*        d_results,
-                              const uint32_t* d_ab2,
-                              const uint32_t* d_crc_tables,
-                              uint8_t*        d_cb_crc_ok,
-                              hipStream_t     stream,
-                              int8_t* const*  d_llr_cbs,
-                              const dm_desc*  d_dm,
-                              int8_t*         d_harq)
+void launch_ldpc_decode_pairs(const dec_group& g, const uint32_t* d_ab2, const dec_launch_args& a)
 {
-  if (nof_groups <= 0) {
+  if (g.count <= 0) {
     return;
   }
-  dim3 grid(nof_groups), block(block_threads);
-#define SRSGPU_PAIRS_LAUNCH1(BG_, MODE_, MAXL_, FUSE_)                                                                  \
-  ldpc_decode_pairs_kernel<BG_, MODE_, MAXL_, 2, FUSE_><<<grid, block, 0, stream>>>(                                   \
-      d_desc, d_llrs, d_out, d_results, d_ab2, d_crc_tables, d_cb_crc_ok, d_llr_cbs, d_dm, d_harq)
-#define SRSGPU_PAIRS_LAUNCH(BG_, MODE_, MAXL_)                                                                         \
-  (d_dm != nullptr ? SRSGPU_PAIRS_LAUNCH1(BG_, MODE_, MAXL_, true) : SRSGPU_PAIRS_LAUNCH1(BG_, MODE_, MAXL_, false))
-  if (bg == 1) {
-    if (max_layers <= 8) {
-      mode == 1 ? SRSGPU_PAIRS_LAUNCH(1, 1, 8) : SRSGPU_PAIRS_LAUNCH(1, 0, 8);
+  dim3 grid(g.count), block(g.threads);
+  with_decoder_class<false>(g.bg, a.mode, g.max_layers, [&](auto BG, auto MODE, auto MAXL) {
+    constexpr int bg = decltype(BG)::value, mode = decltype(MODE)::value, maxl = decltype(MAXL)::value;
+    if (g.d_dm != nullptr) {
+      ldpc_decode_pairs_kernel<bg, mode, maxl, 2, true><<<grid, block, 0, a.stream>>>(
+          g.d_desc, a.d_cw_llrs, a.d_out, a.d_results, d_ab2, a.d_crc_tables, a.d_cb_crc_ok, a.d_harq_cbs, g.d_dm,
+          a.d_harq);
     } else {
-      mode == 1 ? SRSGPU_PAIRS_LAUNCH(1, 1, 16) : SRSGPU_PAIRS_LAUNCH(1, 0, 16);
+      ldpc_decode_pairs_kernel<bg, mode, maxl, 2, false><<<grid, block, 0, a.stream>>>(
+          g.d_desc, a.d_llrs, a.d_out, a.d_results, d_ab2, a.d_crc_tables, a.d_cb_crc_ok, a.d_harq_cbs, nullptr,
+          nullptr);
     }
-  } else {
-    if (max_layers <= 8) {
-      mode == 1 ? SRSGPU_PAIRS_LAUNCH(2, 1, 8) : SRSGPU_PAIRS_LAUNCH(2, 0, 8);
-    } else {
-      mode == 1 ? SRSGPU_PAIRS_LAUNCH(2, 1, 16) : SRSGPU_PAIRS_LAUNCH(2, 0, 16);
-    }
-  }
-#undef SRSGPU_PAIRS_LAUNCH
-#undef SRSGPU_PAIRS_LAUNCH1
+  });
 }
 
 } // namespace srsgpu

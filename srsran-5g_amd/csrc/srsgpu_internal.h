@@ -52,7 +52,7 @@ struct dm_desc {
   uint8_t  Qm;           ///< Modulation order.
   uint8_t  new_data;     ///< First transmission: copy instead of combine.
   uint32_t cb_index;     ///< Codeblock index (CRC flag slot).
-  uint32_t tb_index;     ///< TB fold (launch_ldpc_decode_pk d_tbs): the flag slot of the codeblock's transport block,
+  uint32_t tb_index;     ///< TB fold (dec_launch_args::d_tbs): the flag slot of the codeblock's transport block,
   uint32_t tb_offset;    ///< its first byte in the TB buffer
   uint32_t tb_bytes;     ///< and its size: the first tb_bytes bytes of the decoded message.
   uint64_t r_magic;      ///< ceil(2^40 / (E / Qm)): exact n / R as (n * r_magic) >> 40 for n < 2^20.
@@ -240,72 +240,58 @@ int debug_read_decoder_profile(uint64_t* dst, size_t n);
 int debug_read_decoder_profile_pk(uint64_t* dst, size_t n);
 #endif
 
-/// Launches the packed two-rows-per-lane LDPC decoder (ldpc_decoder_pk.hip; even Z, block_threads >= Z / 2, or
-/// >= 2 x 64 ceil(Z / 128) with split = 2) built for at most max_layers layers (8, 16 or all; every codeblock of the
-/// launch must satisfy layers_bound() <= it). split = 2: each row's edges are shared by two halves of the workgroup
-/// (block_threads a multiple of 128: a half is whole waves).
-/// d_tbs / d_tb_crc_ok (fused launches, optional): every codeblock of the launch is the only one of its transport
-/// block; the decoder then does the TB stage's work itself (pusch_tb.hip with one codeblock): a codeblock whose CRC
-/// passes also writes the first dm_desc::tb_bytes bytes of its message to d_tbs + tb_offset and sets
-/// d_tb_crc_ok[tb_index]; one that fails clears the flag and leaves the TB bytes alone.
-void launch_ldpc_decode_pk(int             bg,
-                           int             mode,
-                           int             max_layers,
-                           int             split,
-                           const dec_desc* d_desc,
-                           int             nof_cbs,
-                           int             block_threads,
-                           const int8_t*   d_llrs,
-                           uint8_t*        d_out,
-                           int32_t*        d_results,
-                           const uint32_t* d_ab,
-                           const uint32_t* d_crc_tables,
-                           uint8_t*        d_cb_crc_ok,
-                           const dm_desc*  d_dm,
-                           int8_t*         d_harq,
-                           hipStream_t     stream,
-                           int8_t* const*  d_harq_cbs  = nullptr,
-                           uint8_t*        d_tbs       = nullptr,
-                           uint8_t*        d_tb_crc_ok = nullptr);
+/// One launch of a decoder plan: the codeblocks of one (base graph, kernel, layer bound). Even lifting sizes go to the
+/// packed two-rows-per-lane kernel (64 * ceil(Z / 128) lanes) built for at most max_layers layers, odd ones to the
+/// one-row-per-lane kernel (64 * ceil(Z / 64) lanes).
+struct dec_group {
+  int       bg         = 1;
+  bool      packed     = false;
+  int       max_layers = 0;   ///< packed: 8, 16 or all; every codeblock of the launch satisfies layers_bound() <= it
+  int       split      = 1;   ///< 2: edge-split kernel (each row's edges over two wave halves), see upload_decoder_plan
+  int       pack       = 1;   ///< 2: two-codeblock workgroups (count = workgroups), see pair_layout_for
+  int       threads    = 64;  ///< workgroup size
+  int       count      = 0;   ///< workgroups
+  dec_desc* d_desc     = nullptr;
+  dm_desc*  d_dm       = nullptr;  ///< Fused rate dematching (DEC_FLAG_FUSED_DM): one dm_desc per codeblock, in order.
+};
 
-/// Launches the two-codeblock packed decoder (ldpc_decode_pairs_kernel): workgroup w decodes d_desc[2 w + i] (slots
-/// with nof_llr = 0 are empty; the two slots share Z, scaling, iteration limit and CRC mode), codeblock slot i on lanes
-/// [i Z / 2, (i + 1) Z / 2), block_threads >= (used slots) x Z / 2. d_ab2: the interleaved image's pair constants. d_dm:
-/// fused rate dematching of first transmissions (d_dm[2 w + i], d_llrs the codeword LLRs, soft buffers at d_harq +
-/// harq_offset or d_llr_cbs[cb]).
-void launch_ldpc_decode_pairs(int             bg,
-                              int             mode,
-                              int             max_layers,
-                              const dec_desc* d_desc,
-                              int             nof_groups,
-                              int             block_threads,
-                              const int8_t*   d_llrs,
-                              uint8_t*        d_out,
-                              int32_t*        d_results,
-                              const uint32_t* d_ab2,
-                              const uint32_t* d_crc_tables,
-                              uint8_t*        d_cb_crc_ok,
-                              hipStream_t     stream,
-                              int8_t* const*  d_llr_cbs = nullptr,
-                              const dm_desc*  d_dm      = nullptr,
-                              int8_t*         d_harq    = nullptr);
+/// What all launches of one execution of a decoder plan share.
+struct dec_launch_args {
+  int             mode         = 1;        ///< 0: generic arithmetic, 1: SIMD arithmetic (SRSGPU_LDPC_IMPL_*)
+  const int8_t*   d_llrs       = nullptr;  ///< decoder input of the unfused groups: codeblock at dec_desc::llr_offset
+  const int8_t*   d_cw_llrs    = nullptr;  ///< codeword LLRs, the input of the fused groups (dm_desc::llr_offset)
+  uint8_t*        d_out        = nullptr;  ///< hard decisions (dec_desc::out_offset)
+  int32_t*        d_results    = nullptr;  ///< per codeblock (dec_desc::cb_index): iterations, 0 skipped, < 0 failed
+  const uint32_t* d_crc_tables = nullptr;  ///< the context's CRC arena
+  uint8_t*        d_cb_crc_ok  = nullptr;  ///< HARQ context (optional): codeblock CRC flags, read (skip) and written
+  int8_t*         d_harq       = nullptr;  ///< fused groups: the HARQ buffer they write (dm_desc::harq_offset)
+  /// Optional per-codeblock HARQ soft buffers in a persistent arena: codeblock c's buffer is d_harq_cbs[c] (c =
+  /// dec_desc::cb_index), the input of an unfused codeblock instead of d_llrs + llr_offset and the output of a fused one
+  /// instead of d_harq + harq_offset.
+  int8_t* const*  d_harq_cbs   = nullptr;
+  /// TB fold (one-codeblock packed kernel, fused groups, optional): every codeblock of the launch is the only one of its
+  /// transport block; the decoder then does the TB stage's work itself (pusch_tb.hip with one codeblock): a codeblock
+  /// whose CRC passes also writes the first dm_desc::tb_bytes bytes of its message to d_tbs + tb_offset and sets
+  /// d_tb_crc_ok[tb_index]; one that fails clears the flag and leaves the TB bytes alone.
+  uint8_t*        d_tbs        = nullptr;
+  uint8_t*        d_tb_crc_ok  = nullptr;
+  hipStream_t     stream       = nullptr;
+};
 
-/// Launches the batched LDPC decoder (ldpc_decoder.hip). d_llr_cbs (optional): codeblock c's input is
-/// d_llr_cbs[dec_desc::cb_index] instead of d_llrs + llr_offset (the same for the packed launchers: per-codeblock HARQ
-/// soft buffers in a persistent arena).
-void launch_ldpc_decode(int                bg,
-                        int                mode,
-                        const dec_desc*    d_desc,
-                        int                nof_cbs,
-                        int                block_threads,
-                        const int8_t*      d_llrs,
-                        uint8_t*           d_out,
-                        int32_t*           d_results,
-                        const uint32_t*    d_shifts,
-                        const uint32_t*    d_crc_tables,
-                        uint8_t*           d_cb_crc_ok,
-                        hipStream_t        stream,
-                        int8_t* const*     d_llr_cbs = nullptr);
+/// Launches the packed two-rows-per-lane LDPC decoder (ldpc_decoder_pk.hip; even Z, g.threads >= Z / 2, or
+/// >= 2 x 64 ceil(Z / 128) with g.split = 2: a multiple of 128, a half is whole waves). d_ab: the pair address
+/// constants of the base graph. A group with d_dm dematches its first transmissions itself (a.d_cw_llrs in, a.d_harq or
+/// a.d_harq_cbs out).
+void launch_ldpc_decode_pk(const dec_group& g, const uint32_t* d_ab, const dec_launch_args& a);
+
+/// Launches the two-codeblock packed decoder (ldpc_decode_pairs_kernel): workgroup w decodes d_desc[2 w + i] (and
+/// d_dm[2 w + i]; slots with nof_llr = 0 are empty; the two slots share Z, scaling, iteration limit and CRC mode),
+/// codeblock slot i on lanes [i Z / 2, (i + 1) Z / 2), g.threads >= (used slots) x Z / 2, g.max_layers <= 16. d_ab2:
+/// the interleaved image's pair constants.
+void launch_ldpc_decode_pairs(const dec_group& g, const uint32_t* d_ab2, const dec_launch_args& a);
+
+/// Launches the one-row-per-lane LDPC decoder (ldpc_decoder.hip; never fused). d_shifts: the base graph's shift table.
+void launch_ldpc_decode(const dec_group& g, const uint32_t* d_shifts, const dec_launch_args& a);
 
 /// PDSCH modulator (pdsch_modulator.hip): per-transmission descriptor.
 struct mod_desc {

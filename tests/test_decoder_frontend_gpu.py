@@ -7,7 +7,8 @@ Every codeblock is compared bit for bit (HARQ soft buffer, iteration count, deco
 composition (chain_lib.oracle_pusch_cb_decode) and with the unfused plan (decoder_fused_dematch=0). The shapes are the
 small ones at which a path changes: Z % 16 == 0 (all fast paths), Z % 8 == 0 only (Z = 104: groups of four, per-bit hard
 decisions), Z % 8 != 0 (per-byte front end), fillers that are / are not multiples of 4 (the latter leave the dword
-path), 64QAM (never the dword path).
+path), 64QAM (never the dword path). The two-codeblock kernel shares the front end: its lifting sizes (Z = 144..192)
+run it with two codeblocks, and with one and an empty slot, per workgroup.
 
 A PUSCH plan hands the decoder whole lifted columns (capi.cpp add_pusch_cb: the input length is rounded up to a
 multiple of Z), so for these plans every group of four lies below `full`; where the rate-matched length ends relative
@@ -86,10 +87,11 @@ def _case(srsgpu, shape, good, bg, Z, qm, E, F):
                                  max_iterations=max_iter)
 
 
-def _check_group(orc, ctx, cbs, llrs, seed, dec_type="avx2", mode=1):
+def _check_group(orc, ctx, cbs, llrs, seed, dec_type="avx2", mode=1, pairs=False):
     """Fused and unfused plans over a HARQ buffer of random old content against each other and the oracle; the fused plan
     with the kernel the host picks for so few codeblocks (the edge-split one) and with the one-row-pair kernel of large
-    launches pinned (decoder_split=0). Returns the oracle's CRC outcomes."""
+    launches pinned (decoder_split=0); with `pairs` also the fused plan of two-codeblock workgroups (decoder_pairs=1,
+    decoder_split=0: Z = 144..192 go to ldpc_decode_pairs_kernel). Returns the oracle's CRC outcomes."""
     import srsgpu
     rng = np.random.default_rng(seed)
     inits = [rng.integers(-127, 128, BG_N_SHORT[c.base_graph] * c.lifting_size).astype(np.int8) for c in cbs]
@@ -100,7 +102,11 @@ def _check_group(orc, ctx, cbs, llrs, seed, dec_type="avx2", mode=1):
         res_p, harq_p, crc_p = dec.decode(llrs, cbs, harq=init.copy())
     with ctx.options(decoder_fused_dematch=0):
         res_u, harq_u, crc_u = dec.decode(llrs, cbs, harq=init.copy())
-    for harq_x, crc_x in ((harq_u, crc_u), (harq_p, crc_p)):
+    others = [(res_p, harq_p, crc_p), (res_u, harq_u, crc_u)]
+    if pairs:
+        with ctx.options(decoder_pairs=1, decoder_split=0):
+            others.append(dec.decode(llrs, cbs, harq=init.copy()))
+    for _, harq_x, crc_x in others:
         assert np.array_equal(harq_f, harq_x)
         assert np.array_equal(np.asarray(crc_f), np.asarray(crc_x))
     off, oks = 0, []
@@ -109,7 +115,7 @@ def _check_group(orc, ctx, cbs, llrs, seed, dec_type="avx2", mode=1):
         N = h0.size
         assert np.array_equal(harq_f[off:off + N], h2), (i, c)
         off += N
-        for res in (res_f, res_p, res_u):
+        for res in [res_f] + [o[0] for o in others]:
             r_g, bits_g = res[i]
             assert (r_g if r_g is not None else -1) == r, (i, c, r_g, r)
             if bits is not None:
@@ -139,6 +145,33 @@ def test_lifting_sizes_and_modulations(orc, ctx, dec_type, mode):
         llrs.append(_payload_llrs(orc, rng, bg, Z, qm, E, F))
     oks = _check_group(orc, ctx, cbs, llrs, 1201, dec_type, mode)
     assert sum(oks[2::3]) >= 12, oks[2::3]
+
+
+def test_two_codeblock_workgroups(orc, ctx):
+    """The fused front end in the two-codeblock kernel (decoder_pairs=1), which shares it with the one-codeblock kernel:
+    Z = 144, 160, 176, 192 (every lifting size that kernel takes), both base graphs in both of its layer classes (the
+    code rate sets the class), each with 256QAM and 4 fillers (groups of four), 256QAM and 6 fillers (symbol by symbol,
+    one 8-byte read per symbol) and 64QAM (symbol by symbol, byte reads). Nine codeblocks per Z, decodable and noise
+    mixed: codeblocks pair when they share Z, early stop and iteration limit, so some workgroups carry two codeblocks
+    and, the count being odd, at least one has an empty slot."""
+    import srsgpu
+    rng = np.random.default_rng(1250)
+    cbs, llrs = [], []
+    for k, (bg, Z, rate, layers) in enumerate(((1, 144, 0.6, 16), (2, 160, 0.4, 16), (1, 176, 0.75, 8), (2, 192, 0.6, 8))):
+        for g, (qm, F) in enumerate(((8, 4), (8, 6), (6, 0))):
+            E = _pick_E(bg, Z, qm, F, rate=rate)
+            # The layer class the host derives (capi.cpp add_pusch_cb, layer_class); above 16 layers the one-codeblock
+            # kernel would take the codeblock.
+            bound = max(-(-(E + F) // Z) + 2, BG_K[bg] + 4) - BG_K[bg]
+            assert (8 if bound <= 8 else 16 if bound <= 16 else 0) == layers, (bg, Z, bound)
+            for good in (True, False, True):
+                cbs.append(_case(srsgpu, 3 * k + g, good, bg, Z, qm, E, F))
+                llrs.append(_payload_llrs(orc, rng, bg, Z, qm, E, F) if good and len(cbs) % 3 == 0
+                            else _llrs(rng, E, good))
+    for Z in (144, 160, 176, 192):
+        keys = [(c.use_early_stop, c.max_iterations) for c in cbs if c.lifting_size == Z]
+        assert len(keys) % 2 == 1 and max(keys.count(x) for x in keys) >= 2, keys
+    _check_group(orc, ctx, cbs, llrs, 1251, pairs=True)
 
 
 def test_input_end_and_fillers(orc, ctx):

@@ -128,6 +128,49 @@ def test_decoder_edge_cases(orc, ctx, variant):
             assert (r if r is not None else -1) == r0 and np.array_equal(b, b0), (sf, dec_type)
 
 
+@pytest.fixture(scope="module")
+def partial_column_cases(orc):
+    """Inputs that end inside a lifted column, n_nodes * Z + r LLRs with r = 1, 15, Z / 2, Z - 1 and non-zero LLRs up
+    to the end, with the oracle's results: (1, 192) (the two-codeblock kernel's size), (1, 384), (2, 10) (r = 15 is a
+    column and a half), each from the shortest input the decoder accepts to the all-layers class. The LLRs of the
+    partial column are scaled up to +/-120: there the decoder keeps the reference LLR range, while whole columns are
+    clamped to +/-64 (ldpc_decoder_impl.cpp:152)."""
+    import srsgpu
+    rng = np.random.default_rng(4100)
+    llrs, cfgs, polys, want = [], [], [], []
+    for bg, Z in ((1, 192), (1, 384), (2, 10)):
+        K, N = BG_K[bg], BG_N_SHORT[bg]
+        for j, r in enumerate((1, 15, Z // 2, Z - 1)):
+            for t, n_nodes in enumerate((K + 2, K + 9, N - 2)):
+                n = n_nodes * Z + r
+                assert (K + 2) * Z < n <= N * Z and n % Z != 0
+                _, _, llr = encode_with_llrs(orc, rng, bg, Z, crc_poly=CRC24B, amp=10,
+                                             noise=[3.0, 5.0, 7.0, 9.0][(j + t) % 4], n_llr=n)
+                tail = llr[n - n % Z:].astype(np.int32)
+                tail[tail == 0] = 1
+                llr[n - n % Z:] = np.sign(tail) * np.clip(6 * np.abs(tail), 65, 120)
+                assert np.abs(llr[n - n % Z:]).min() > 64
+                cfg = srsgpu.CodeblockDecodeConfig(bg, Z, nof_crc_bits=24, max_iterations=6)
+                r0, bits = orc.ldpc_decode(1, bg, Z, llr, nof_crc_bits=24, crc_poly=CRC24B, max_iter=6, scaling=0.8)
+                llrs.append(llr)
+                cfgs.append(cfg)
+                polys.append(CRC24B)
+                want.append((None if r0 < 0 else r0, bits))
+        assert any(w[0] is not None for w in want[-12:]), (bg, Z)  # at least one of the shape decodes
+    return llrs, cfgs, polys, want
+
+
+def test_decoder_partial_trailing_column(ctx, variant, partial_column_cases):
+    """Input lengths that are no multiple of Z, in one batch per kernel variant: the packed kernels zero the positions
+    past the input in the partly filled column and do not clamp the LLRs inside it. Against the oracle, bit-exact."""
+    import srsgpu
+    llrs, cfgs, polys, want = partial_column_cases
+    got = srsgpu.LdpcDecoder(ctx, "avx2").decode_batch(llrs, cfgs, polys)
+    for i, ((r_g, b_g), (r_w, b_w)) in enumerate(zip(got, want)):
+        assert r_g == r_w, (i, cfgs[i], llrs[i].size, r_g, r_w)
+        assert np.array_equal(b_g, b_w), (i, cfgs[i], llrs[i].size)
+
+
 def test_decoder_rejects_invalid_configs(ctx):
     import srsgpu
     dec = srsgpu.LdpcDecoder(ctx, "avx2")

@@ -7,6 +7,7 @@ Pinned against the reference's own dmrs_pusch_estimator_impl + port_channel_esti
 interpolator, DFT time-alignment estimator) built from its sources (oracle/ref/ref_pusch_chest.cpp in
 oracle/_ref/libsrsref.so) by tests/test_oracle_vs_reference.py and tests/golden/pusch_chest.npz. The reference computes
 in float32 (AVX2), the restatement in float64: estimates and noise variances agree within a stated tolerance.
+`estimate_layers` (at the end) restates the GPU estimator's 2-4 layer extension, which the reference cannot pin.
 
 Reference files (under /root/reference/lib/phy/):
   upper/signal_processors/dmrs_pusch_estimator_impl.cpp:69   DM-RS sequence: c_init = ((14 n_slot + l + 1)
@@ -126,6 +127,9 @@ def fd_smoothing(pilots, nof_rb, stride, strategy):
     nv = min(MAX_V_PILOTS, taps.size // 2)
     if nof_rb == 1:
         nv = pilots.size
+    # Never more virtual pilots than pilots (2 RB of type 2: 8 pilots under a 21-tap filter; the reference takes the
+    # first 10 of a span of 8 there, which is undefined).
+    nv = min(nv, pilots.size)
     enlarged = np.concatenate([virtual_pilots(pilots[:nv], True), pilots, virtual_pilots(pilots[-nv:], False)])
     return np.convolve(enlarged, taps, mode="same")[nv: nv + pilots.size]
 
@@ -320,3 +324,103 @@ def estimate(cfg, grid, fd="filter", td="average", compensate_cfo=False, numerol
             for i, rb in enumerate(rbs):
                 ch[p, l, rb * 12: (rb + 1) * 12] = fr[i * 12: (i + 1) * 12]
     return ch, nvar, rsrp, epre, dict(cfo_hz=cfo_hz, ta_s=ta_s, cfo_phase=cfo_ph)
+
+
+def group_pattern(dmrs_type2, group):
+    """RE pattern of CDM group `group` within a PRB (dmrs_helper.cpp: type 1 delta = group, type 2 delta = 2 group)."""
+    if dmrs_type2:
+        return [2 * group + (j & 1) + 6 * (j >> 1) for j in range(4)]
+    return [group + 2 * j for j in range(6)]
+
+
+def estimate_layers(cfg, grid, nof_layers=1, fd="filter", td="average", compensate_cfo=False, numerology=1,
+                    crb_mask=None):
+    """Multi-layer extension of `estimate` (DM-RS ports 1000 .. 1000 + L - 1; the reference estimates one layer, so this
+    restates the operation srsran-5g_amd/csrc/pusch_chest.hip documents, not reference code). Returns
+    (ch (L, P, 14, nsc) complex128, noise_var (P,), rsrp (P,), epre (P,), extra) with extra = dict(cfo_hz (P,), ta_s (P,), cfo_hz_groups
+    (ngroups, P)); nof_layers = 1 is `estimate` itself.
+
+    Per rx port and CDM group g = 0 .. (L + 1) // 2 - 1, GL = min(2, L - 2 g) layers: the pilots at group_pattern(g),
+    the LSE y conj(pilot) with the base sequence of layer 0 (indexed by pilot number, no cover code), the CFO from the
+    group's own LSEs of the first two DM-RS symbols (derotating its LSEs and rotating its output estimates when
+    compensating), the planes sum / (beta D) ("average") or one per DM-RS symbol over beta ("interpolate"). GL = 2: the
+    frequency cover code w_f = (+1, -1) of the group's second layer is removed over the pilot pairs (2j, 2j + 1),
+    h0 = (a + b) / 2 and h1 = (a - b) / 2, each written to both pilots of the pair (the channel taken as flat over the
+    pair); every layer is then smoothed on its own (virtual pilots and filter as for one layer) and interpolated with
+    the group's offset (g for type 1, 2 g for type 2) and the type's stride. Only group 0 gives metrics: EPRE of its
+    received pilots, RSRP of layer 0's smoothed planes, the noise residual against beta / Q sum_q (F0_q +- F1_q)
+    (- on odd pilots, re-rotated by the group's CFO when compensating) normalised as in `estimate`, the time alignment
+    of layer 0's planes. Output layer 2 g + ly is layer ly of group g."""
+    L = int(nof_layers)
+    if L == 1:
+        ch, nvar, rsrp, epre, ex = estimate(cfg, grid, fd, td, compensate_cfo, numerology, crb_mask)
+        return ch[None], nvar, rsrp, epre, dict(cfo_hz=ex["cfo_hz"], ta_s=ex["ta_s"],
+                                                cfo_hz_groups=ex["cfo_hz"][None].copy())
+    if not 2 <= L <= 4:
+        raise ValueError(L)
+    P = cfg["nof_rx_ports"]
+    t2 = cfg["dmrs_type2"]
+    beta = cfg["scaling"]
+    stride = 1 if t2 else 2
+    rb0, nrb = cfg["rb_start"], cfg["nof_rb"]
+    rbs = list(range(rb0, rb0 + nrb)) if crb_mask is None else [int(i) for i in np.flatnonzero(crb_mask)]
+    contiguous = rbs[-1] - rbs[0] + 1 == len(rbs)
+    nrb = len(rbs)
+    first, last = cfg["start_symbol"], cfg["start_symbol"] + cfg["nof_symbols"]
+    syms = [l for l in range(first, last) if (cfg["dmrs_symbol_mask"] >> l) & 1]
+    Dn = len(syms)
+    pil = [dmrs_sequence(cfg["slot"], l, cfg["scrambling_id"], cfg["n_scid"], t2, rb0, nrb, rbs) for l in syms]
+    N = pil[0].size
+    ep = symbol_start_epochs(numerology)
+    scs_hz = (15 << numerology) * 1000.0
+    ngroups = (L + 1) // 2
+    ch = np.zeros((L, P, 14, grid.shape[2]), np.complex128)
+    nvar, rsrp, epre = np.zeros(P), np.zeros(P), np.zeros(P)
+    ta_s, cfo_groups = np.zeros(P), np.full((ngroups, P), np.nan)
+    odd = np.arange(N) % 2 == 1
+    for p in range(P):
+        for g in range(ngroups):
+            GL = min(2, L - 2 * g)
+            pat = group_pattern(t2, g)
+            sc = np.array([rb * 12 + k for rb in rbs for k in pat])
+            rx = [grid[p, l, sc].astype(np.complex128) for l in syms]
+            lse = [r * np.conj(q) for r, q in zip(rx, pil)]
+            cfo = None
+            if Dn > 1:
+                cfo = float(np.angle(np.dot(np.conj(lse[0]), lse[1]))) / (2 * np.pi) / (ep[syms[1]] - ep[syms[0]])
+                cfo_groups[g, p] = cfo * scs_hz
+                if compensate_cfo:
+                    lse = [y * np.exp(-2j * np.pi * ep[l] * cfo) for y, l in zip(lse, syms)]
+            rotate = compensate_cfo and cfo is not None
+            raw = [sum(lse) / (beta * Dn)] if td == "average" else [y / beta for y in lse]
+            Q = len(raw)
+            if GL == 2:
+                layers = [[np.repeat((f[0::2] + f[1::2]) / 2, 2) for f in raw],
+                          [np.repeat((f[0::2] - f[1::2]) / 2, 2) for f in raw]]
+            else:
+                layers = [raw]
+            planes = [[fd_smoothing(f, nrb, stride, fd) for f in ly] for ly in layers]
+            if g == 0:
+                epre[p] = sum(np.sum(np.abs(r) ** 2) for r in rx) / (N * Dn)
+                rsrp[p] = sum(np.sum(np.abs(f) ** 2) for f in planes[0]) * beta * beta * Dn / Q / (N * Dn)
+                h = sum(planes[0])
+                if GL == 2:
+                    h = h + np.where(odd, -1.0, 1.0) * sum(planes[1])
+                h = h * beta / Q
+                noise = 0.0
+                for r, q, l in zip(rx, pil, syms):
+                    pred = h * q
+                    if rotate:
+                        pred = pred * np.exp(2j * np.pi * ep[l] * cfo)
+                    noise += np.sum(np.abs(r - pred) ** 2)
+                nvar[p] = max(rsrp[p] / 1e10, noise / (N * Dn - 1))
+                ta_s[p] = estimate_ta(planes[0], sc, numerology, stride if contiguous else 1)
+            for ly in range(GL):
+                frs = [interpolate(f, pat[0], stride, nrb * 12) for f in planes[ly]]
+                for l in range(first, last):
+                    fr = frs[0] if td == "average" else td_interpolate(frs, syms, first, last, l)
+                    if rotate:
+                        fr = fr * np.exp(2j * np.pi * ep[l] * cfo)
+                    for i, rb in enumerate(rbs):
+                        ch[2 * g + ly, p, l, rb * 12: (rb + 1) * 12] = fr[i * 12: (i + 1) * 12]
+    return ch, nvar, rsrp, epre, dict(cfo_hz=cfo_groups[0].copy(), ta_s=ta_s, cfo_hz_groups=cfo_groups)

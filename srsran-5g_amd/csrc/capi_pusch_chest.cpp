@@ -234,6 +234,12 @@ int srsgpu_pusch_chest_plan_create_ex(srsgpu_context*                  ctx,
     if (c.nof_rb == 1) {
       nof_v = per_rb;
     }
+    // Never more virtual pilots than pilots to extrapolate them from: 2 RB of type 2 hold 8 pilots under a 21-tap
+    // filter (10 virtual pilots per edge would be regressed over LDS outside the band's pilots). This is the project's
+    // own rule, not the reference's: the reference takes the first 10 of a span of 8 pilots there, which is undefined
+    // (add_v_pilots, port_channel_estimator_helpers.cpp:364). It extends the reference's 1-RB rule above, and the taps
+    // past the virtual pilots see zeros as they do for 1 RB. Only this geometry reaches it.
+    nof_v = std::min<unsigned>(nof_v, c.nof_rb * per_rb);
     const unsigned ngroups = (L + 1) / 2;
     // Symbol epochs and the "interpolate" plane table (apply_td_domain_strategy, :509): for symbol l the planes of the
     // DM-RS symbols around it (or the first / last two), and the weight of the second.

@@ -166,7 +166,7 @@ def equalize(rx, H, noise_var, mmse=False):
         nvar = np.where(good, nvar_acc * rcp * rcp, np.inf).astype(F)
         return eq[:, None], nvar[:, None]
     if L == 2 and not mmse and P in (2, 4):
-        nve = F(np.max(nv))
+        nve = F(np.max(nv[:P]))
         if not (_isnormal(nve) and nve >= 0):
             return np.zeros((n, 2), np.complex64), np.full((n, 2), np.inf, F)
         norm = [np.sum([(H[p, l].real ** 2 + H[p, l].imag ** 2).astype(F) for p in range(P)], axis=0).astype(F)
@@ -191,20 +191,35 @@ def equalize(rx, H, noise_var, mmse=False):
 def equalize_mmse(rx, H, noise_var):
     """Extension beyond the reference (parity unpinned): linear MMSE for L layers, float64, unbiased output.
     A = H^H H + nv I, x = diag(G)^-1 A^-1 H^H y with G = I - nv A^-1, nvar_l = nv [A^-1]_ll / g_l;
-    nv = max over ports (like the reference's multi-layer paths)."""
+    nv = max over the P ports' noise variances (like the reference's multi-layer paths; entries of noise_var past the
+    first P are never read). One batched inverse over the REs.
+
+    Validity rule (the project's own: no reference defines multi-layer MMSE, this is what the GPU kernel does, stated
+    after the reference's ZF paths, which give a symbol of 0 and an infinite variance where their denominator is not a
+    normal number): an RE's layer is valid when g_l and nv [A^-1]_ll are both normal positive float32 numbers;
+    otherwise eq = 0 and nvar = inf, so that its LLRs are 0 and the statistics skip it. noise_var = 0 (or a maximum
+    that is not a normal positive number) therefore invalidates every layer of every RE. A layer whose channel
+    column is zero has g_l = 1 - nv / nv, zero up to rounding: either way its symbol is exactly 0 (H^H y is) and its
+    LLRs are 0; whether its huge variance counts as infinite is left to the rounding."""
     P, L, n = H.shape
-    nv = float(np.max(noise_var))
     eq = np.zeros((n, L), np.complex128)
-    var = np.zeros((n, L))
-    for i in range(n):
-        h = H[:, :, i].astype(np.complex128)
-        A = h.conj().T @ h + nv * np.eye(L)
-        Ai = np.linalg.inv(A)
-        x = Ai @ (h.conj().T @ rx[:, i].astype(np.complex128))
-        g = 1 - nv * np.real(np.diag(Ai))
-        eq[i] = x / g
-        var[i] = nv * np.real(np.diag(Ai)) / g
-    return eq, var
+    var = np.full((n, L), np.inf)
+    nv = float(np.max(np.asarray(noise_var, np.float64)[:P]))
+    if not (_isnormal(nv) and nv > 0):
+        return eq, var
+    h = np.transpose(H, (2, 0, 1)).astype(np.complex128)  # (n, P, L)
+    hh = np.conj(np.transpose(h, (0, 2, 1)))
+    m = hh @ np.transpose(rx, (1, 0)).astype(np.complex128)[:, :, None]  # (n, L, 1)
+    Ai = np.linalg.inv(hh @ h + nv * np.eye(L))
+    x = (Ai @ m)[:, :, 0]
+    naii = nv * np.real(np.diagonal(Ai, axis1=1, axis2=2))
+    g = 1 - naii
+    ok = _isnormal(g) & (g > 0) & _isnormal(naii) & (naii > 0)
+    gs = np.where(ok, g, 1)
+    # A layer with a zero channel column has a symbol of exactly zero (A is block diagonal there); the inverse's
+    # rounding must not be divided by a g of rounding size.
+    x = np.where(np.all(h == 0, axis=1), 0, x)
+    return np.where(ok, x / gs, 0), np.where(ok, naii / gs, np.inf)
 
 
 def data_res(start_symbol, nof_symbols, dmrs_symbol_mask, dmrs_type2, nof_cdm_groups_without_data, rb_start, nof_rb):

@@ -814,6 +814,53 @@ int srsgpu_ulsch_demux_plan_execute(const srsgpu_ulsch_demux_plan* plan,
 void srsgpu_ulsch_demux_plan_destroy(srsgpu_ulsch_demux_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * UCI decoder, short blocks — replaces srsran::uci_decoder::decode(span<const log_likelihood_ratio> llr,
+ * const configuration& config) (include/srsran/phy/upper/channel_processors/uci/uci_decoder.h) for messages of 1..11
+ * bits, which uci_decoder_impl::decode hands to the short-block detector
+ * (lib/phy/upper/channel_processors/uci/uci_decoder_impl.cpp:119), for every field of a batch in one launch. Restates
+ * short_block_detector_impl::detect (lib/phy/upper/channel_coding/short/short_block_detector_impl.cpp:186) bit for
+ * bit: the validation on the count of non-zero LLRs (:60), the rate dematching with a saturating sum per block (:160,
+ * as the AVX2 build sums LLRs, log_likelihood_ratio.cpp:432), the 1-bit sign decision, the 2-bit search (:89) and the
+ * 3..11-bit maximum-likelihood search with the GLRT validity threshold (:129, :221). Input LLRs lie in [-120, 120], as
+ * the PUSCH demodulator writes them. Fields of 12 bits and more (polar code) are rejected: they stay with the host.
+ * A field reads its LLRs from one of three input streams, so that a plan decodes the UL-SCH demultiplexer's HARQ-ACK,
+ * CSI Part 1 and CSI Part 2 streams where they lie (source 0, 1, 2 with llr_offset = that plan's harq_offset,
+ * csi1_offset, csi2_offset).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint8_t  nof_bits;         /* A: message bits, 1..11 */
+  uint8_t  modulation_order; /* Qm: 1, 2, 4, 6, 8 (the block before rate matching: Qm, 3 Qm or 32 bits) */
+  uint8_t  source;           /* input stream of the field: 0, 1 or 2 (d_src0 / d_src1 / d_src2) */
+  uint8_t  reserved;
+  uint32_t nof_enc_bits;     /* E: encoded LLRs of the field (0: the field comes out invalid) */
+  uint32_t llr_offset;       /* first LLR of the field in its input stream */
+} srsgpu_uci_field_config;
+
+typedef struct srsgpu_uci_decoder_plan srsgpu_uci_decoder_plan;
+
+/** Validates the fields and uploads their descriptors. SRSGPU_ERR_INVALID_ARG for nof_bits = 0, nof_bits > 11 (polar
+ *  coded UCI is not implemented), a modulation_order outside {1, 2, 4, 6, 8}, source > 2 or nof_enc_bits > 2^24 (far
+ *  above any PUSCH's capacity). Blocking. */
+int srsgpu_uci_decoder_plan_create(srsgpu_context*                ctx,
+                                   const srsgpu_uci_field_config* cfgs,
+                                   uint32_t                       nof_fields,
+                                   srsgpu_uci_decoder_plan**      plan);
+
+/** Decodes every planned field: d_msgs[f] bit j = message bit j of field f (bits nof_bits and above 0; every message
+ *  bit 1 for a field that fails the validation, as the reference fills it), d_status[f] = 1 valid / 0 invalid (the
+ *  detector's return value). Input streams no field reads may be NULL. Asynchronous on `stream`, no allocation,
+ *  hipGraph-capturable. */
+int srsgpu_uci_decoder_plan_execute(const srsgpu_uci_decoder_plan* plan,
+                                    const int8_t*                  d_src0,
+                                    const int8_t*                  d_src1,
+                                    const int8_t*                  d_src2,
+                                    uint16_t*                      d_msgs,
+                                    uint8_t*                       d_status,
+                                    void*                          stream);
+
+void srsgpu_uci_decoder_plan_destroy(srsgpu_uci_decoder_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PUSCH decoder (transport-block level) — replaces srsran::pusch_decoder (include/srsran/phy/upper/channel_processors/
  * pusch/pusch_decoder.h; lib/phy/upper/channel_processors/pusch/pusch_decoder_impl.cpp: new_data :98, segmentation
  * :190, codeblock tasks :283, join_and_notify :386): segmentation, per-codeblock rate dematching + HARQ combining +

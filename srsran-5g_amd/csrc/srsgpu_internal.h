@@ -616,6 +616,27 @@ void launch_ulsch_demux(const ulsch_demux_desc*  d_desc,
                         const uint32_t*          d_seq,
                         hipStream_t              stream);
 
+/// UCI short-block decoder (uci_decoder.hip): one field of 1..11 message bits, decoded by one wavefront.
+struct uci_field_desc {
+  uint32_t llr_offset;   ///< First of the field's LLRs in its source stream.
+  uint32_t nof_enc;      ///< E: encoded (rate-matched) LLRs.
+  uint8_t  nof_bits;     ///< A: 1..11.
+  uint8_t  qm;           ///< Modulation order: 1, 2, 4, 6, 8.
+  uint8_t  source;       ///< Input stream 0..2.
+  uint8_t  min_nonzero;  ///< Fewer non-zero LLRs than this: invalid (calculate_uci_min_encoded_bits, uci_info.h:85).
+  uint8_t  threshold;    ///< GLRT threshold of A (short_block_detector_impl.cpp:221).
+  uint8_t  pad[3];
+};
+
+void launch_uci_decode(const uci_field_desc* d_desc,
+                       uint32_t              nof_fields,
+                       const int8_t*         d_src0,
+                       const int8_t*         d_src1,
+                       const int8_t*         d_src2,
+                       uint16_t*             d_msgs,
+                       uint8_t*              d_status,
+                       hipStream_t           stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

@@ -254,6 +254,22 @@ class UlschDemuxConfig(ctypes.Structure):
 assert ctypes.sizeof(UlschDemuxConfig) == 64
 
 
+class UciFieldConfig(ctypes.Structure):
+    """srsgpu_uci_field_config (include/srsgpu_phy.h): one UCI field of 1..11 bits, its modulation order, its input
+    stream (0..2) and where its E encoded LLRs start there."""
+    _fields_ = [
+        ("nof_bits", ctypes.c_uint8),
+        ("modulation_order", ctypes.c_uint8),
+        ("source", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+        ("nof_enc_bits", ctypes.c_uint32),
+        ("llr_offset", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(UciFieldConfig) == 12
+
+
 class PuschChestConfig(ctypes.Structure):
     """srsgpu_pusch_chest_config (include/srsgpu_phy.h): dmrs_pusch_estimator::configuration of one transmission."""
     _fields_ = [
@@ -374,6 +390,10 @@ def load_library(path: str = LIB_PATH):
     lib.srsgpu_ulsch_demux_plan_execute.argtypes = [P, P, P, P, P, P, P]
     lib.srsgpu_ulsch_demux_plan_destroy.argtypes = [P]
     lib.srsgpu_ulsch_demux_plan_destroy.restype = None
+    lib.srsgpu_uci_decoder_plan_create.argtypes = [P, P, ctypes.c_uint32, ctypes.POINTER(P)]
+    lib.srsgpu_uci_decoder_plan_execute.argtypes = [P, P, P, P, P, P, P]
+    lib.srsgpu_uci_decoder_plan_destroy.argtypes = [P]
+    lib.srsgpu_uci_decoder_plan_destroy.restype = None
     lib.srsgpu_pusch_chest_plan_create_ex.argtypes = [P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.POINTER(P)]
     lib.srsgpu_pdsch_dmrs_plan_destroy.argtypes = [P]
@@ -448,6 +468,7 @@ EXPORTED_SYMBOLS = [
     "srsgpu_pusch_chest_plan_create_ex", "srsgpu_ulsch_demux_plan_create", "srsgpu_ulsch_demux_plan_nof_llrs",
     "srsgpu_ulsch_demux_plan_symbol_llrs", "srsgpu_harq_copy_arenas",
     "srsgpu_ulsch_demux_plan_execute", "srsgpu_ulsch_demux_plan_destroy",
+    "srsgpu_uci_decoder_plan_create", "srsgpu_uci_decoder_plan_execute", "srsgpu_uci_decoder_plan_destroy",
     "srsgpu_pusch_chest_plan_create", "srsgpu_pusch_chest_plan_execute", "srsgpu_pusch_chest_plan_destroy",
     "srsgpu_pusch_chest_plan_execute_copy",
     "srsgpu_pdsch_dmrs_plan_create", "srsgpu_pdsch_dmrs_plan_create_ex", "srsgpu_pdsch_dmrs_plan_execute", "srsgpu_pdsch_dmrs_plan_destroy",
@@ -1493,6 +1514,71 @@ class UlschDemultiplexer:
                         for j, k in enumerate(("sch", "harq", "csi1", "csi2"))})
         plan.close()
         return res
+
+
+class UciDecoderPlan:
+    """srsgpu_uci_decoder_plan: short-block UCI fields (1..11 bits) decoded in one launch. fields: UciFieldConfig
+    entries, or (nof_bits, modulation_order, source, nof_enc_bits, llr_offset) tuples."""
+
+    def __init__(self, ctx: Context, fields):
+        self.ctx = ctx
+        self.nof_fields = len(fields)
+        arr = (UciFieldConfig * max(len(fields), 1))()
+        for i, f in enumerate(fields):
+            if isinstance(f, UciFieldConfig):
+                arr[i] = f
+            else:
+                a = arr[i]
+                a.nof_bits, a.modulation_order, a.source, a.nof_enc_bits, a.llr_offset = f
+        h = ctypes.c_void_p()
+        _check(_lib.srsgpu_uci_decoder_plan_create(ctx.handle, ctypes.cast(arr, ctypes.c_void_p), len(fields),
+                                                   ctypes.byref(h)))
+        self.handle = h
+
+    def execute(self, d_harq, d_csi1, d_csi2, d_msgs, d_status, stream=None):
+        """Inputs: the three int8 LLR streams (sources 0, 1, 2; None where no field reads one). Outputs: d_msgs
+        (int16 / uint16, bit j = message bit j) and d_status (uint8, 1 valid) per field."""
+        _check(_lib.srsgpu_uci_decoder_plan_execute(self.handle, _dptr(d_harq), _dptr(d_csi1), _dptr(d_csi2),
+                                                    _dptr(d_msgs), _dptr(d_status), _stream_handle(stream)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.srsgpu_uci_decoder_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class UciDecoder:
+    """GPU counterpart of srsran::short_block_detector::detect (short_block_detector_impl.cpp:186), which
+    uci_decoder_impl::decode uses for messages of up to 11 bits: decode_batch() takes each field's LLRs, number of
+    message bits and modulation order and returns (list of uint8 bit arrays, list of valid flags)."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    def decode_batch(self, llrs_list: Sequence[np.ndarray], nof_bits: Sequence[int],
+                     modulation_orders: Sequence[int]):
+        dev = torch.device("cuda", self.ctx.device)
+        fields, o = [], 0
+        for llrs, a, qm in zip(llrs_list, nof_bits, modulation_orders):
+            fields.append((int(a), int(qm), 0, int(np.asarray(llrs).size), o))
+            o += int(np.asarray(llrs).size)
+        plan = UciDecoderPlan(self.ctx, fields)
+        host = np.concatenate([np.asarray(x, np.int8).ravel() for x in llrs_list] + [np.zeros(4, np.int8)])
+        d_in = torch.from_numpy(host).to(dev)
+        d_msgs = torch.zeros(max(len(fields), 1), dtype=torch.int16, device=dev)
+        d_status = torch.zeros(max(len(fields), 1), dtype=torch.uint8, device=dev)
+        plan.execute(d_in, None, None, d_msgs, d_status)
+        torch.cuda.synchronize(dev)
+        msgs, status = d_msgs.cpu().numpy().view(np.uint16), d_status.cpu().numpy()
+        plan.close()
+        bits = [((int(m) >> np.arange(int(a))) & 1).astype(np.uint8) for m, a in zip(msgs, nof_bits)]
+        return bits, [bool(v) for v in status[: len(fields)]]
 
 
 class OfdmPlan:

@@ -861,6 +861,58 @@ int srsgpu_uci_decoder_plan_execute(const srsgpu_uci_decoder_plan* plan,
 void srsgpu_uci_decoder_plan_destroy(srsgpu_uci_decoder_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * UCI decoder, polar-coded fields — replaces srsran::uci_decoder::decode for messages of 12..1706 bits, which
+ * uci_decoder_impl::decode hands to decode_codeword_polar
+ * (lib/phy/upper/channel_processors/uci/uci_decoder_impl.cpp:119, :43), for every field of a batch in one launch, one
+ * wavefront per codeblock. Restates the chain bit for bit: segmentation into one or two codeblocks and the 6- / 11-bit
+ * CRC (include/srsran/ran/uci/uci_info.h:40, :54; uci_decoder_impl.cpp:58-69), the uplink polar code of (K, E) with
+ * nMax = 10 (lib/phy/upper/channel_coding/polar/polar_code_impl.cpp:325, :421), the rate dematching with the promotion
+ * sum in the reference's order (polar_rate_dematcher_impl.cpp:100, lib/phy/upper/log_likelihood_ratio.cpp:75), the
+ * simplified successive-cancellation decoder (polar_decoder_impl.cpp:335), the de-allocation
+ * (polar_deallocator_impl.cpp:27) and the CRC over all K bits of a codeblock (uci_decoder_impl.cpp:107). Input LLRs lie
+ * in [-120, 120] or are +-127, as log_likelihood_ratio holds them. Together with srsgpu_uci_decoder_plan (1..11 bits)
+ * this covers uci_decoder::decode.
+ *
+ * One rule differs: both codeblocks of a two-codeblock field are always decoded and their bits written. The reference
+ * decodes codeblock 1 only when codeblock 0 passes its CRC (uci_decoder_impl.cpp:65) and otherwise leaves the caller's
+ * bits untouched, so no value of those bits is the reference's; the status is invalid either way.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint16_t nof_bits;         /* A: message bits, 12..1706 */
+  uint8_t  source;           /* input stream of the field: 0, 1 or 2 (d_src0 / d_src1 / d_src2) */
+  uint8_t  reserved;
+  uint32_t nof_enc_bits;     /* E: encoded LLRs of the field; two codeblocks read floor(E / 2) each */
+  uint32_t llr_offset;       /* first LLR of the field in its input stream */
+  uint32_t msg_word_offset;  /* first of the field's ceil(A / 32) words in d_msgs */
+} srsgpu_uci_polar_field_config;
+
+typedef struct srsgpu_uci_polar_decoder_plan srsgpu_uci_polar_decoder_plan;
+
+/** Validates the fields, builds the tables of every distinct code once and uploads them. SRSGPU_ERR_INVALID_ARG, with a
+ *  message naming the field and the reason, for what the reference's assertions refuse: nof_bits outside 12..1706
+ *  (uci_decoder_impl.cpp:124, uci_decoder_impl.h:74), source > 2, more than 8192 encoded bits per codeblock
+ *  (polar_code_impl.cpp:334), K + nPC >= E per codeblock (:363), K >= N or K outside 18..25 / 31..1023 (:407, :345;
+ *  neither can follow from a nof_bits in range), and fields whose message words overlap. Blocking. */
+int srsgpu_uci_polar_decoder_plan_create(srsgpu_context*                      ctx,
+                                         const srsgpu_uci_polar_field_config* cfgs,
+                                         uint32_t                             nof_fields,
+                                         srsgpu_uci_polar_decoder_plan**      plan);
+
+/** Decodes every planned field: message bit j of field f is bit j mod 32 of d_msgs[msg_word_offset + j / 32] (the
+ *  field's last word is written whole, zeros above bit A - 1; words of no field are not written), d_status[f] = 1 when
+ *  the CRC of every codeblock passes (uci_status::valid), else 0. Input streams no field reads may be NULL.
+ *  Asynchronous on `stream`, no allocation, hipGraph-capturable. */
+int srsgpu_uci_polar_decoder_plan_execute(const srsgpu_uci_polar_decoder_plan* plan,
+                                          const int8_t*                        d_src0,
+                                          const int8_t*                        d_src1,
+                                          const int8_t*                        d_src2,
+                                          uint32_t*                            d_msgs,
+                                          uint8_t*                             d_status,
+                                          void*                                stream);
+
+void srsgpu_uci_polar_decoder_plan_destroy(srsgpu_uci_polar_decoder_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PUSCH decoder (transport-block level) — replaces srsran::pusch_decoder (include/srsran/phy/upper/channel_processors/
  * pusch/pusch_decoder.h; lib/phy/upper/channel_processors/pusch/pusch_decoder_impl.cpp: new_data :98, segmentation
  * :190, codeblock tasks :283, join_and_notify :386): segmentation, per-codeblock rate dematching + HARQ combining +

@@ -637,6 +637,39 @@ void launch_uci_decode(const uci_field_desc* d_desc,
                        uint8_t*              d_status,
                        hipStream_t           stream);
 
+/// UCI polar decoder (uci_polar_decoder.hip): one field of 12..1706 message bits, one wavefront per codeblock. The
+/// tables of a distinct (K, E) are built on the host (polar_code.h) and shared by every codeblock with that code.
+struct uci_polar_code_desc {
+  uint32_t ops_offset;    ///< First op of the decoder schedule in the plan's op buffer.
+  uint32_t nof_ops;
+  uint32_t demap_offset;  ///< Composed dematching map in the plan's 16-bit table buffer: R rows of N entries.
+  uint32_t info_offset;   ///< There too: the K message positions, then the K CRC weights.
+  uint16_t K;             ///< Message, filler and CRC bits per codeblock.
+  uint8_t  n;             ///< log2 N, 5..10.
+  uint8_t  R;             ///< Rows of the dematching map: max(1, ceil(E / N)) <= 32.
+};
+struct uci_polar_field_desc {
+  uint32_t llr_offset;       ///< First of the field's LLRs in its source stream.
+  uint32_t E_cb;             ///< LLRs per codeblock (uci_decoder_impl.cpp:59); codeblock 1 starts E_cb further.
+  uint32_t msg_word_offset;  ///< First output word.
+  uint32_t code;             ///< Index of the field's uci_polar_code_desc.
+  uint16_t nof_bits;         ///< A: 12..1706.
+  uint8_t  source;           ///< Input stream 0..2.
+  uint8_t  nof_cb;           ///< Codeblocks: 1 or 2 (uci_info.h:40).
+};
+
+void launch_uci_polar_decode(const uci_polar_field_desc* d_fields,
+                             uint32_t                    nof_fields,
+                             const uci_polar_code_desc*  d_codes,
+                             const uint32_t*             d_ops,
+                             const uint16_t*             d_tables,
+                             const int8_t*               d_src0,
+                             const int8_t*               d_src1,
+                             const int8_t*               d_src2,
+                             uint32_t*                   d_msgs,
+                             uint8_t*                    d_status,
+                             hipStream_t                 stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

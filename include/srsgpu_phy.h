@@ -376,6 +376,71 @@ int srsgpu_pdsch_dmrs_plan_execute(const srsgpu_pdsch_dmrs_plan* plan, uint32_t*
 void srsgpu_pdsch_dmrs_plan_destroy(srsgpu_pdsch_dmrs_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PDCCH — replaces srsran::pdcch_processor::process(resource_grid_writer& grid, const pdu_t& pdu)
+ * (include/srsran/phy/upper/channel_processors/pdcch/pdcch_processor.h, lib/phy/upper/channel_processors/pdcch/
+ * pdcch_processor_impl.cpp:79) for every DCI of a batch of slots, in one launch: the CCE to PRB mapping
+ * (lib/ran/pdcch/cce_to_prb_mapping.cpp, at plan creation), DCI encoding (pdcch_encoder_impl.cpp: CRC24C with the RNTI,
+ * the downlink polar code, rate matching), scrambling, QPSK and mapping (pdcch_modulator_impl.cpp) and the DM-RS
+ * (signal_processors/dmrs_pdcch_processor_impl.cpp), into bf16 grids of the PDSCH modulator's layout. Bit-exact with
+ * the reference. Only the REs of the DCIs' PRBs on the CORESET symbols are written.
+ *
+ * Precoding is one layer and one PRG: a weight per port. The reference's generic mapper does not define per-PRG
+ * precoding for an allocation below its top PRG (resource_grid_mapper_impl.cpp:225). Powers are linear amplitudes, as
+ * in the PDSCH configurations: data_scaling is pdcch_modulator::config_t::scaling (applied when it is a normal float),
+ * dmrs_amplitude is dmrs_pdcch_processor::config_t::amplitude; the dB fields of the PDU are converted by the caller.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t frequency_resources; /* coreset_description: bit i set = the 6-PRB frequency resource i (45 bits) */
+  uint32_t bwp_size_rb;
+  uint32_t bwp_start_rb;
+  uint32_t start_symbol_index;
+  uint32_t duration;            /* 1..3 symbols */
+  uint32_t cce_to_reg_mapping;  /* 0 CORESET0, 1 non-interleaved, 2 interleaved */
+  uint32_t reg_bundle_size;     /* interleaved only: 2 or 6 (duration 1, 2), 3 or 6 (duration 3) */
+  uint32_t interleaver_size;    /* interleaved only: 2, 3 or 6 */
+  uint32_t shift_index;         /* interleaved: n_shift; CORESET0: the cell identity */
+  uint32_t slot_index;          /* n_slot within the frame (pdu_t::slot) */
+  uint32_t rnti;                /* dci_description: scrambles the CRC */
+  uint32_t n_id_pdcch_dmrs;
+  uint32_t n_id_pdcch_data;
+  uint32_t n_rnti;
+  uint32_t cce_index;
+  uint32_t aggregation_level;   /* 1, 2, 4, 8 or 16 */
+  uint32_t nof_ports;           /* 1..grid_nof_ports */
+  float    data_scaling;        /* linear amplitude of the data REs */
+  float    dmrs_amplitude;      /* linear amplitude of the DM-RS REs */
+  float    precoding[4][2];     /* [port] (re, im) */
+  uint32_t payload_offset;      /* byte offset of the payload in d_payloads; bits packed MSB first */
+  uint32_t nof_payload_bits;    /* 12..128, and fewer than 108 * aggregation_level - 24 */
+  uint32_t grid_index;          /* resource grid (slot) the DCI is mapped into, < nof_grids */
+  uint32_t reserved;
+} srsgpu_pdcch_config;
+
+typedef struct srsgpu_pdcch_plan srsgpu_pdcch_plan;
+
+/** Refuses, with the reference's reason as the message, what pdcch_processor_validator_impl::is_valid, the polar
+ *  code (36 <= K <= 164, K < E) and the CCE mapper's assertion refuse; a PRB outside the BWP or the grid; ports outside
+ *  1..grid_nof_ports; and two DCIs that write the same REs (one launch gives them no order). */
+int srsgpu_pdcch_plan_create(srsgpu_context*            ctx,
+                             const srsgpu_pdcch_config* cfgs,
+                             uint32_t                   nof_dcis,
+                             uint32_t                   grid_nof_prb,
+                             uint32_t                   grid_nof_ports,
+                             uint32_t                   nof_grids,
+                             srsgpu_pdcch_plan**        plan);
+
+/** Encodes and maps every planned DCI: reads the payloads from d_payloads (payload_bytes bytes, device memory, so a
+ *  captured graph carries new DCIs on every replay) and writes d_grids (uint32 per RE: re | im << 16). One launch,
+ *  asynchronous on `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_pdcch_plan_execute(const srsgpu_pdcch_plan* plan,
+                              const uint8_t*           d_payloads,
+                              uint64_t                 payload_bytes,
+                              uint32_t*                d_grids,
+                              void*                    stream);
+
+void srsgpu_pdcch_plan_destroy(srsgpu_pdcch_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

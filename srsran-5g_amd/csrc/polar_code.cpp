@@ -1,7 +1,9 @@
-// Uplink polar code construction for the UCI polar decoder plan; see polar_code.h. Written from TS 38.212 sections
-// 5.3.1.2 (n, the frozen and parity-check sets) and 5.4.1.1 (sub-block interleaver, bit selection, channel interleaver)
-// and the reference's behaviour where it departs from the text (noted at each place).
+// Uplink polar code construction for the UCI polar decoder plan and downlink construction for the PDCCH plan; see
+// polar_code.h. Written from TS 38.212 sections 5.3.1.1 (input interleaver), 5.3.1.2 (n, the frozen and parity-check
+// sets) and 5.4.1.1 (sub-block interleaver, bit selection, channel interleaver) and the reference's behaviour where it
+// departs from the text (noted at each place).
 #include "polar_code.h"
+#include "polar_dl_tables.h"
 #include "polar_tables.h"
 #include <algorithm>
 
@@ -50,7 +52,8 @@ struct schedule_builder {
 
 } // namespace
 
-uint32_t polar_code_size_log(uint32_t K, uint32_t E)
+/// log2 of the mother code size for an uplink (n_max_log = 10) or downlink (9) code (polar_code_impl.cpp:365-404).
+static uint32_t size_log(uint32_t K, uint32_t E, uint32_t n_max_log)
 {
   uint32_t e = 1;
   while ((1u << e) < E) {
@@ -61,7 +64,56 @@ uint32_t polar_code_size_log(uint32_t K, uint32_t E)
   while (k < 10 && (1u << k) < K) {
     ++k;
   }
-  return std::max(5u, std::min({n1, k + 3, N_MAX_LOG}));
+  return std::max(5u, std::min({n1, k + 3, n_max_log}));
+}
+
+uint32_t polar_code_size_log(uint32_t K, uint32_t E)
+{
+  return size_log(K, E, N_MAX_LOG);
+}
+
+/// Sub-block interleaver and the `count` most reliable positions the rate matching leaves usable, increasing
+/// reliability (polar_code_impl.cpp:426-456), shared by the uplink and downlink constructions.
+static void reliable_set(uint32_t K, uint32_t E, uint32_t n, uint32_t count, std::vector<uint16_t>& interleaver,
+                         std::vector<uint16_t>& k_set)
+{
+  const uint32_t N = 1u << n;
+  // Sub-block interleaver, section 5.4.1.1: J(i) = P(floor(32 i / N)) N / 32 + i mod (N / 32).
+  interleaver.resize(N);
+  for (uint32_t i = 0; i < N; ++i) {
+    interleaver[i] = static_cast<uint16_t>(kPolarSubblockPattern[32 * i / N] * (N / 32) + i % (N / 32));
+  }
+
+  // Frozen set, section 5.3.1.2: positions that the rate matching drops (the first N - E after interleaving when
+  // puncturing, 16 K <= 7 E, with a further low range; the last N - E when shortening) cannot carry information.
+  std::vector<uint8_t> excluded(N, 0);
+  const bool           puncture = E < N && 16 * K <= 7 * E;
+  const bool           shorten  = E < N && !puncture;
+  if (puncture) {
+    // The reference excludes positions 0..T (polar_code_impl.cpp:440-445, :306): for E < 3 N / 4 that is one more than
+    // the ceil(9 N / 16 - E / 4) of the specification. Restated as the reference behaves.
+    const uint32_t T = E >= 3 * N / 4 ? 3 * N / 4 - E / 2 - 1 : 9 * N / 16 - E / 4;
+    for (uint32_t i = 0; i < N - E; ++i) {
+      excluded[interleaver[i]] = 1;
+    }
+    for (uint32_t q = 0; q <= T && q < N; ++q) {
+      excluded[q] = 1;
+    }
+  } else if (shorten) {
+    for (uint32_t i = E; i < N; ++i) {
+      excluded[interleaver[i]] = 1;
+    }
+    excluded[0] = 1;  // T = 0 in the reference's set difference (:306).
+  }
+  // The `count` most reliable of the remaining positions, least reliable first.
+  k_set.clear();
+  for (int i = 1023; i >= 0 && k_set.size() < count; --i) {
+    const uint16_t q = kPolarReliabilitySequence[i];
+    if (q < N && excluded[q] == 0) {
+      k_set.push_back(q);
+    }
+  }
+  std::reverse(k_set.begin(), k_set.end());
 }
 
 const char* polar_code_refusal(uint32_t K, uint32_t E)
@@ -94,42 +146,10 @@ void polar_code_build(uint32_t K, uint32_t E, polar_code& code)
   code.nWmPC = (code.nPC > 0 && E > K + 189) ? 1 : 0;
   const uint32_t N = 1u << code.n;
 
-  // Sub-block interleaver, section 5.4.1.1: J(i) = P(floor(32 i / N)) N / 32 + i mod (N / 32).
-  code.interleaver.resize(N);
-  for (uint32_t i = 0; i < N; ++i) {
-    code.interleaver[i] = static_cast<uint16_t>(kPolarSubblockPattern[32 * i / N] * (N / 32) + i % (N / 32));
-  }
-
-  // Frozen set, section 5.3.1.2: positions that the rate matching drops (the first N - E after interleaving when
-  // puncturing, 16 K <= 7 E, with a further low range; the last N - E when shortening) cannot carry information.
-  std::vector<uint8_t> excluded(N, 0);
-  const bool           puncture = E < N && 16 * K <= 7 * E;
-  const bool           shorten  = E < N && !puncture;
-  if (puncture) {
-    // The reference excludes positions 0..T (polar_code_impl.cpp:440-445, :306): for E < 3 N / 4 that is one more than
-    // the ceil(9 N / 16 - E / 4) of the specification. Restated as the reference behaves.
-    const uint32_t T = E >= 3 * N / 4 ? 3 * N / 4 - E / 2 - 1 : 9 * N / 16 - E / 4;
-    for (uint32_t i = 0; i < N - E; ++i) {
-      excluded[code.interleaver[i]] = 1;
-    }
-    for (uint32_t q = 0; q <= T && q < N; ++q) {
-      excluded[q] = 1;
-    }
-  } else if (shorten) {
-    for (uint32_t i = E; i < N; ++i) {
-      excluded[code.interleaver[i]] = 1;
-    }
-    excluded[0] = 1;  // T = 0 in the reference's set difference (:306).
-  }
-  // The K + nPC most reliable of the remaining positions, least reliable first.
   std::vector<uint16_t> k_set;
-  for (int i = 1023; i >= 0 && k_set.size() < K + code.nPC; --i) {
-    const uint16_t q = kPolarReliabilitySequence[i];
-    if (q < N && excluded[q] == 0) {
-      k_set.push_back(q);
-    }
-  }
-  std::reverse(k_set.begin(), k_set.end());
+  reliable_set(K, E, code.n, K + code.nPC, code.interleaver, k_set);
+  const bool puncture = E < N && 16 * K <= 7 * E;
+  const bool shorten  = E < N && !puncture;
   code.frozen.assign(N, 1);
   for (uint16_t q : k_set) {
     code.frozen[q] = 0;
@@ -202,6 +222,60 @@ void polar_code_build(uint32_t K, uint32_t E, polar_code& code)
     if ((power >> order) != 0) {
       power ^= poly;
     }
+  }
+}
+
+const char* polar_dl_code_refusal(uint32_t K, uint32_t E)
+{
+  if (K < 36 || K > POLAR_DL_K_MAX) {
+    return "K (payload and CRC bits) outside 36..164";
+  }
+  if (K >= E) {
+    return "K does not fit the encoded bits";
+  }
+  if (E > E_MAX) {
+    return "more than 8192 encoded bits";
+  }
+  return nullptr;
+}
+
+void polar_dl_code_build(uint32_t K, uint32_t E, polar_dl_code& code)
+{
+  code   = polar_dl_code{};
+  code.K = K;
+  code.E = E;
+  code.n = size_log(K, E, 9);
+  const uint32_t N = 1u << code.n;
+
+  std::vector<uint16_t> interleaver, k_set;
+  reliable_set(K, E, code.n, K, interleaver, k_set);
+  code.frozen.assign(N, 1);
+  for (uint16_t q : k_set) {
+    code.frozen[q] = 0;
+  }
+
+  // Input interleaver (polar_interleaver_impl.cpp:45): the pattern entries of at least 164 - K, in table order, less
+  // 164 - K: c'[k] = c[pi[k]].
+  for (uint32_t m = 0; m < POLAR_DL_K_MAX; ++m) {
+    if (kPolarInputInterleaverPattern[m] >= POLAR_DL_K_MAX - K) {
+      code.input_interleaver.push_back(static_cast<uint8_t>(kPolarInputInterleaverPattern[m] - (POLAR_DL_K_MAX - K)));
+    }
+  }
+
+  // Allocation (polar_allocator_impl.cpp: no parity-check bits, increasing position) composed with it.
+  code.u_source.assign(N, POLAR_DL_FROZEN);
+  uint32_t k = 0;
+  for (uint32_t q = 0; q < N; ++q) {
+    if (code.frozen[q] == 0) {
+      code.u_source[q] = code.input_interleaver[k++];
+    }
+  }
+
+  // Sub-block interleaver and bit selection (polar_rate_matcher_impl.cpp:41), no channel interleaver.
+  const bool puncture = E < N && 16 * K <= 7 * E;
+  code.gather.resize(E);
+  for (uint32_t j = 0; j < E; ++j) {
+    code.gather[j] = interleaver[E >= N ? j % N : puncture ? j + (N - E) : j];
   }
 }
 

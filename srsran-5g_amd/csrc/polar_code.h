@@ -1,7 +1,8 @@
 // Host-side construction of the uplink polar code (nMax = 10) of TS 38.212 sections 5.3.1.2 and 5.4.1.1 for the UCI
 // polar decoder plan (capi_uci_polar_decoder.cpp, uci_polar_decoder.hip): everything the kernel reads as tables is
 // fixed here at plan creation, per distinct (K, E). No HIP call in this translation unit, so that a host-only program
-// can check it (tools/polar_code_check.cpp).
+// can check it (tools/polar_code_check.cpp). The downlink code (nMax = 9) of the PDCCH plan is built here too, from the
+// same frozen-set rules (polar_dl_code below; tools/pdcch_code_check.cpp).
 //
 // Reference (behaviour, not code): lib/phy/upper/channel_coding/polar/polar_code_impl.cpp:325 (set_code_params), :421
 // (set); the three dematching steps of polar_rate_dematcher_impl.cpp:100 composed into one table; the node types and
@@ -52,6 +53,31 @@ uint32_t polar_code_size_log(uint32_t K, uint32_t E);
 
 /// Fills `code` for an accepted (K, E).
 void polar_code_build(uint32_t K, uint32_t E, polar_code& code);
+
+/// Downlink polar code (nMax = 9, no parity-check bits, input interleaver, no channel interleaver) of the PDCCH plan
+/// (capi_pdcch.cpp, pdcch.hip). Reference (behaviour, not code): pdcch_encoder_impl.cpp:63 (channel_coding),
+/// polar_code_impl.cpp:325 / :421 with nMax = 9, polar_interleaver_impl.cpp:45, polar_allocator_impl.cpp:27,
+/// polar_rate_matcher_impl.cpp:100 without its channel interleaver.
+constexpr uint32_t POLAR_DL_K_MAX  = 164;   ///< polar_interleaver_impl::K_MAX_IL
+constexpr uint8_t  POLAR_DL_FROZEN = 0xff;  ///< u_source mark of a frozen position.
+
+struct polar_dl_code {
+  uint32_t K = 0, E = 0;
+  uint32_t n = 0;                          ///< log2 of the mother code size N (5..9).
+  std::vector<uint8_t>  frozen;            ///< N entries, 1 = frozen.
+  std::vector<uint8_t>  input_interleaver; ///< K entries: c'[k] = c[input_interleaver[k]] (TS 38.212 Table 5.3.1.1-1).
+  /// Input interleaver and allocation composed: N entries, the index in c of the bit at encoder input position q, or
+  /// POLAR_DL_FROZEN.
+  std::vector<uint8_t>  u_source;
+  /// Sub-block interleaver and bit selection composed: E entries, rate-matched bit j is encoded bit gather[j].
+  std::vector<uint16_t> gather;
+};
+
+/// Why the reference's assertions refuse a downlink (K, E) (polar_code_impl.cpp:334, :339, :363), or nullptr.
+const char* polar_dl_code_refusal(uint32_t K, uint32_t E);
+
+/// Fills `code` for an accepted downlink (K, E).
+void polar_dl_code_build(uint32_t K, uint32_t E, polar_dl_code& code);
 
 /// Codeblocks of a UCI field of A bits in E LLRs (uci_info.h:40, uci_decoder_impl.cpp:49-69).
 struct uci_polar_segmentation {

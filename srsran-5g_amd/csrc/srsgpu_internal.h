@@ -670,6 +670,55 @@ void launch_uci_polar_decode(const uci_polar_field_desc* d_fields,
                              uint8_t*                    d_status,
                              hipStream_t                 stream);
 
+/// PDCCH (pdcch.hip): one DCI, one workgroup. Tables are built per distinct (K, E) at plan creation (polar_code.cpp).
+constexpr uint32_t PDCCH_MAX_PRBS       = 96;   ///< 16 CCEs of 6 REGs on one symbol.
+constexpr uint32_t PDCCH_MAX_DATA_WORDS = 54;   ///< 1728 rate-matched bits.
+constexpr uint32_t PDCCH_MAX_DMRS_WORDS = 52;   ///< 275 PRBs of 3 pilots of 2 bits, per symbol.
+constexpr uint32_t PDCCH_CRC_WEIGHTS    = 152;  ///< x^(24 + j) mod g_CRC24C, j = 0..151 (128 payload bits and 24 ones).
+
+struct pdcch_code_desc {
+  uint32_t u_source_offset;  ///< Into the byte table: N entries, index into c or 0xff (polar_dl_code::u_source).
+  uint32_t gather_offset;    ///< Into the pair table: E / 2 words, gather[2 r] | gather[2 r + 1] << 16.
+  uint16_t K;
+  uint16_t n;
+};
+
+struct pdcch_desc {
+  uint32_t payload_offset;  ///< Bytes into the payload buffer; bits packed MSB first.
+  uint32_t code;
+  uint32_t crc_init;        ///< CRC24C contribution of the 24 leading ones, xor the RNTI.
+  uint32_t c_init_data;
+  uint32_t c_init_dmrs[3];  ///< Per CORESET symbol.
+  uint32_t grid_base;       ///< Element of (port 0, start symbol, subcarrier 0) of the DCI's grid.
+  uint32_t nsc;
+  uint32_t port_stride;
+  uint32_t prb_offset;      ///< Into the PRB table: nof_prb ascending PRBs.
+  uint32_t dmrs_word0;      ///< First DM-RS sequence word any PRB of the DCI reads.
+  uint16_t nof_payload_bits;
+  uint16_t nof_prb;
+  uint16_t dmrs_nof_words;
+  uint16_t reference_rb;    ///< reference_point_k_rb.
+  uint16_t duration;
+  uint16_t nof_ports;
+  float    data_amplitude;  ///< Of one QPSK component: sqrt(1/2), times the scaling when it applies.
+  float    dmrs_amplitude;  ///< Of one DM-RS component: sqrt(1/2) x amplitude.
+  float    w[4][2];
+};
+
+void launch_pdcch(const pdcch_desc*      d_descs,
+                  uint32_t               nof_dcis,
+                  const pdcch_code_desc* d_codes,
+                  const uint8_t*         d_u_source,
+                  const uint32_t*        d_gather,
+                  const uint16_t*        d_prbs,
+                  const uint32_t*        d_crc_weights,
+                  const uint8_t*         d_payloads,
+                  uint32_t*              d_grids,
+                  const uint32_t*        d_x1,
+                  const uint32_t*        d_x2_jump,
+                  const uint32_t*        d_x2_lane,
+                  hipStream_t            stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

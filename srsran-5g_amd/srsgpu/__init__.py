@@ -286,6 +286,40 @@ class UciPolarFieldConfig(ctypes.Structure):
 assert ctypes.sizeof(UciPolarFieldConfig) == 16
 
 
+class PdcchConfig(ctypes.Structure):
+    """srsgpu_pdcch_config (include/srsgpu_phy.h): the CORESET, the DCI, linear amplitudes, one weight per port, where
+    the payload bits lie in the payload buffer and the grid the DCI is mapped into."""
+    _fields_ = [
+        ("frequency_resources", ctypes.c_uint64),
+        ("bwp_size_rb", ctypes.c_uint32),
+        ("bwp_start_rb", ctypes.c_uint32),
+        ("start_symbol_index", ctypes.c_uint32),
+        ("duration", ctypes.c_uint32),
+        ("cce_to_reg_mapping", ctypes.c_uint32),
+        ("reg_bundle_size", ctypes.c_uint32),
+        ("interleaver_size", ctypes.c_uint32),
+        ("shift_index", ctypes.c_uint32),
+        ("slot_index", ctypes.c_uint32),
+        ("rnti", ctypes.c_uint32),
+        ("n_id_pdcch_dmrs", ctypes.c_uint32),
+        ("n_id_pdcch_data", ctypes.c_uint32),
+        ("n_rnti", ctypes.c_uint32),
+        ("cce_index", ctypes.c_uint32),
+        ("aggregation_level", ctypes.c_uint32),
+        ("nof_ports", ctypes.c_uint32),
+        ("data_scaling", ctypes.c_float),
+        ("dmrs_amplitude", ctypes.c_float),
+        ("precoding", ctypes.c_float * 8),
+        ("payload_offset", ctypes.c_uint32),
+        ("nof_payload_bits", ctypes.c_uint32),
+        ("grid_index", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(PdcchConfig) == 128
+
+
 class PuschChestConfig(ctypes.Structure):
     """srsgpu_pusch_chest_config (include/srsgpu_phy.h): dmrs_pusch_estimator::configuration of one transmission."""
     _fields_ = [
@@ -414,6 +448,11 @@ def load_library(path: str = LIB_PATH):
     lib.srsgpu_uci_polar_decoder_plan_execute.argtypes = [P, P, P, P, P, P, P]
     lib.srsgpu_uci_polar_decoder_plan_destroy.argtypes = [P]
     lib.srsgpu_uci_polar_decoder_plan_destroy.restype = None
+    lib.srsgpu_pdcch_plan_create.argtypes = [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.POINTER(P)]
+    lib.srsgpu_pdcch_plan_execute.argtypes = [P, P, ctypes.c_uint64, P, P]
+    lib.srsgpu_pdcch_plan_destroy.argtypes = [P]
+    lib.srsgpu_pdcch_plan_destroy.restype = None
     lib.srsgpu_pusch_chest_plan_create_ex.argtypes = [P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.POINTER(P)]
     lib.srsgpu_pdsch_dmrs_plan_destroy.argtypes = [P]
@@ -494,6 +533,7 @@ EXPORTED_SYMBOLS = [
     "srsgpu_pusch_chest_plan_create", "srsgpu_pusch_chest_plan_execute", "srsgpu_pusch_chest_plan_destroy",
     "srsgpu_pusch_chest_plan_execute_copy",
     "srsgpu_pdsch_dmrs_plan_create", "srsgpu_pdsch_dmrs_plan_create_ex", "srsgpu_pdsch_dmrs_plan_execute", "srsgpu_pdsch_dmrs_plan_destroy",
+    "srsgpu_pdcch_plan_create", "srsgpu_pdcch_plan_execute", "srsgpu_pdcch_plan_destroy",
 ]
 
 
@@ -1184,6 +1224,124 @@ class PdschDmrsPlan:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+@dataclass
+class Pdcch:
+    """pdcch_processor::pdu_t (pdcch_processor.h:134) of one DCI: the CORESET (frequency_resources: bit i set = the 6-PRB
+    resource i; mapping 0 CORESET0, 1 non-interleaved, 2 interleaved), the DCI with its payload bits, linear
+    amplitudes in place of the dB offsets, and one complex precoding weight per port."""
+    bwp_size_rb: int
+    bwp_start_rb: int
+    start_symbol: int
+    duration: int
+    frequency_resources: int
+    mapping: int
+    slot_index: int
+    rnti: int
+    n_id_pdcch_dmrs: int
+    n_id_pdcch_data: int
+    n_rnti: int
+    cce_index: int
+    aggregation_level: int
+    payload: np.ndarray
+    weights: np.ndarray
+    reg_bundle_size: int = 0
+    interleaver_size: int = 0
+    shift_index: int = 0
+    data_scaling: float = 1.0
+    dmrs_amplitude: float = 1.0
+    grid_index: int = 0
+
+
+def pdcch_pack_payloads(dcis: Sequence[Pdcch]):
+    """The DCIs' payload bits packed MSB first, each from a byte boundary: (uint8 buffer, byte offsets)."""
+    chunks, offsets, pos = [], [], 0
+    for d in dcis:
+        packed = np.packbits(np.asarray(d.payload, np.uint8))
+        offsets.append(pos)
+        chunks.append(packed)
+        pos += packed.size
+    return (np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)), offsets
+
+
+def make_pdcch_configs(dcis: Sequence[Pdcch], payload_offsets: Sequence[int]):
+    arr = (PdcchConfig * max(len(dcis), 1))()
+    for a, d, o in zip(arr, dcis, payload_offsets):
+        a.frequency_resources, a.bwp_size_rb, a.bwp_start_rb = d.frequency_resources, d.bwp_size_rb, d.bwp_start_rb
+        a.start_symbol_index, a.duration, a.cce_to_reg_mapping = d.start_symbol, d.duration, d.mapping
+        a.reg_bundle_size, a.interleaver_size, a.shift_index = d.reg_bundle_size, d.interleaver_size, d.shift_index
+        a.slot_index, a.rnti, a.n_id_pdcch_dmrs, a.n_id_pdcch_data = d.slot_index, d.rnti, d.n_id_pdcch_dmrs, d.n_id_pdcch_data
+        a.n_rnti, a.cce_index, a.aggregation_level = d.n_rnti, d.cce_index, d.aggregation_level
+        wc = np.asarray(d.weights, np.complex64).ravel()
+        a.nof_ports = wc.size
+        w = np.zeros((4, 2), np.float32)
+        w[: min(wc.size, 4), 0], w[: min(wc.size, 4), 1] = wc.real[:4], wc.imag[:4]
+        a.precoding[:] = w.reshape(-1).tolist()
+        a.data_scaling, a.dmrs_amplitude = float(d.data_scaling), float(d.dmrs_amplitude)
+        a.payload_offset, a.nof_payload_bits, a.grid_index = o, int(np.asarray(d.payload).size), d.grid_index
+    return arr
+
+
+class PdcchPlan:
+    """srsgpu_pdcch_plan: every DCI of a batch of slots encoded, modulated and mapped with its DM-RS in one launch.
+    dcis: Pdcch entries; payload_offsets: byte offset of each DCI's packed payload in the buffer given to execute()
+    (default: pdcch_pack_payloads order). self.payload_bytes: the least size of that buffer."""
+
+    def __init__(self, ctx: Context, dcis: Sequence[Pdcch], grid_nof_prb: int, grid_nof_ports: int = 4,
+                 nof_grids: Optional[int] = None, payload_offsets: Optional[Sequence[int]] = None):
+        self.ctx = ctx
+        self.nof_dcis = len(dcis)
+        if payload_offsets is None:
+            _, payload_offsets = pdcch_pack_payloads(dcis)
+        if nof_grids is None:
+            nof_grids = max([d.grid_index for d in dcis], default=0) + 1
+        self.nof_grids, self.grid_nof_prb, self.grid_nof_ports = nof_grids, grid_nof_prb, grid_nof_ports
+        self.payload_bytes = max([o + (np.asarray(d.payload).size + 7) // 8 for o, d in zip(payload_offsets, dcis)],
+                                 default=0)
+        arr = make_pdcch_configs(dcis, payload_offsets)
+        h = ctypes.c_void_p()
+        _check(_lib.srsgpu_pdcch_plan_create(ctx.handle, ctypes.cast(arr, ctypes.c_void_p), len(dcis), grid_nof_prb,
+                                             grid_nof_ports, nof_grids, ctypes.byref(h)))
+        self.handle = h
+
+    def execute(self, d_payloads, d_grids, stream=None):
+        """d_payloads: uint8 device tensor of the packed payloads; d_grids: (nof_grids, ports, 14, 12 PRBs) int32 /
+        uint32 words (re | im << 16, bf16). Asynchronous on `stream`."""
+        _check(_lib.srsgpu_pdcch_plan_execute(self.handle, _dptr(d_payloads), int(d_payloads.numel() * d_payloads.element_size()),
+                                              _dptr(d_grids),
+                                              _stream_handle(stream)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.srsgpu_pdcch_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class PdcchProcessor:
+    """GPU counterpart of pdcch_processor_impl::process for a list of DCIs: process_batch() returns the grids as a
+    (nof_grids, ports, 14, 12 PRBs) uint32 array (re | im << 16), every RE no DCI writes holding `fill`."""
+
+    def __init__(self, ctx: Context, grid_nof_prb: int, grid_nof_ports: int = 4):
+        self.ctx, self.grid_nof_prb, self.grid_nof_ports = ctx, grid_nof_prb, grid_nof_ports
+
+    def process_batch(self, dcis: Sequence[Pdcch], nof_grids: Optional[int] = None, fill: int = 0) -> np.ndarray:
+        dev = torch.device("cuda", self.ctx.device)
+        payloads, offsets = pdcch_pack_payloads(dcis)
+        plan = PdcchPlan(self.ctx, dcis, self.grid_nof_prb, self.grid_nof_ports, nof_grids, offsets)
+        d_payloads = torch.from_numpy(np.concatenate([payloads, np.zeros(1, np.uint8)])).to(dev)
+        host = np.full((plan.nof_grids, self.grid_nof_ports, 14, 12 * self.grid_nof_prb), fill, np.uint32)
+        d_grids = torch.from_numpy(host.view(np.int32)).to(dev)
+        plan.execute(d_payloads, d_grids)
+        torch.cuda.synchronize(dev)
+        plan.close()
+        return d_grids.cpu().numpy().view(np.uint32)
 
 
 @dataclass

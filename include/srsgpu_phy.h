@@ -1147,6 +1147,10 @@ int srsgpu_pusch_chest_plan_execute_copy(const srsgpu_pusch_chest_plan* plan,
 int srsgpu_pusch_decoder_plan_enable_timing(srsgpu_pusch_decoder_plan* plan, int enable);
 int srsgpu_pusch_decoder_plan_stage_times(srsgpu_pusch_decoder_plan* plan, float* ms, uint32_t* nof_executes);
 
+/** Number of device allocations that the contexts and plans of this process hold at the moment of the call. A plan's
+ *  create followed by its destroy leaves it unchanged, and so does a create that fails (lifetime tests). */
+int64_t srsgpu_debug_live_device_buffers(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,21 +62,21 @@ struct srsgpu_pusch_cb_plan {
   std::vector<crc_key>      crc_refs;  ///< CRC tables referenced (top-level plans only).
   srsgpu_context*           ctx     = nullptr;
   int                       impl    = SRSGPU_LDPC_IMPL_SIMD;
-  dm_desc*                  d_dm    = nullptr;
+  device_buffer<dm_desc>    d_dm;
   int                       nof_cbs = 0;
-  srsgpu_ldpc_decoder_plan* dec     = nullptr;
+  plan_ptr<srsgpu_ldpc_decoder_plan> dec;
 };
 
 struct srsgpu_pdsch_encoder_plan {
   std::vector<crc_key> crc_refs;  ///< CRC tables referenced.
   mutable stage_timer timer;
   srsgpu_context* ctx        = nullptr;
-  tb_crc_desc*    d_tb       = nullptr;
-  uint32_t*       d_tb_crc   = nullptr;
-  tb_crc_slice*   d_slices   = nullptr;  ///< tb_crc_kernel work (TBs split into TB_CRC_SLICE_BYTES ranges).
+  device_buffer<tb_crc_desc>  d_tb;
+  device_buffer<uint32_t>     d_tb_crc;
+  device_buffer<tb_crc_slice> d_slices;  ///< tb_crc_kernel work (TBs split into TB_CRC_SLICE_BYTES ranges).
   int             nof_slices = 0;
   int             nof_tbs    = 0;
-  enc_desc*       d_enc[2]   = {nullptr, nullptr};  ///< Per base graph: byte-kernel codeblocks, then packed ones.
+  device_buffer<enc_desc> d_enc[2];  ///< Per base graph: byte-kernel codeblocks, then packed ones.
   int             count[2]   = {0, 0};
   int             count_pk[2] = {0, 0};
   bool            inline_tb_crc = false;  ///< Every codeblock packed, every TB CRC table cached, every TB at most
@@ -95,12 +95,12 @@ struct srsgpu_pusch_decoder_plan {
   mutable stage_timer   timer;      ///< Three stages (enable_timing 1).
   mutable stage_timer   timer_dec;  ///< The decoding stage only (enable_timing 2): two events per execute.
   srsgpu_context*       ctx     = nullptr;
-  srsgpu_pusch_cb_plan* cbs     = nullptr;
-  tb_dec_desc*          d_tb    = nullptr;
+  plan_ptr<srsgpu_pusch_cb_plan> cbs;
+  device_buffer<tb_dec_desc> d_tb;
   int                   nof_tbs = 0;
   int                   tb_threads = 256;  ///< pusch_tb_kernel workgroup size (1024 for large TBs).
-  tb_slice*             d_slices   = nullptr;  ///< Sliced TB stage (large segmented TBs): pusch_tb_slice_kernel.
-  uint32_t*             d_tb_acc   = nullptr;  ///< Per-TB CRC sums and slice counters (zero between executes).
+  device_buffer<tb_slice> d_slices;  ///< Sliced TB stage (large segmented TBs): pusch_tb_slice_kernel.
+  device_buffer<uint32_t> d_tb_acc;  ///< Per-TB CRC sums and slice counters (zero between executes).
   int                   nof_slices = 0;
   /// Every TB has one codeblock and every codeblock runs in a fused one-codeblock decoder launch: the decoder writes the
   /// TBs and their flags (dec_launch_args::d_tbs) and execute launches no TB stage
@@ -113,6 +113,9 @@ struct srsgpu_ldpc_decoder_plan {
   srsgpu_context*    ctx  = nullptr;
   int                impl = SRSGPU_LDPC_IMPL_SIMD;
   std::vector<dec_group> groups;  ///< One kernel launch per (base graph, kernel, layer bound).
+  /// Owners of groups[i].d_desc and groups[i].d_dm (null when the group is not fused).
+  std::vector<device_buffer<dec_desc>> group_descs;
+  std::vector<device_buffer<dm_desc>>  group_dms;
   uint64_t           input_llrs = 0;  ///< LLR bytes the decoder moves per execute: dec_desc::nof_llr per codeblock,
                                       ///< E + N for fused ones (codeword LLRs read, HARQ buffer written).
 };
@@ -229,7 +232,7 @@ int get_crc_table(srsgpu_context* ctx, int poly, int L, uint32_t& offset, std::v
       r ^= g;
     }
   }
-  if (hipMemcpy(ctx->d_crc_arena + off, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
+  if (hipMemcpy(ctx->d_crc_arena.get() + off, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
       hipSuccess) {
     crc_free_block(ctx, off, words);
     return fail(SRSGPU_ERR_HIP, "CRC table upload failed");
@@ -346,7 +349,7 @@ int srsgpu_context_create(int device, srsgpu_context** out)
     return fail(SRSGPU_ERR_INVALID_ARG, "device %d not present (%d HIP devices)", device, ndev);
   }
   HIP_TRY(hipSetDevice(device));
-  auto* ctx   = new srsgpu_context();
+  std::unique_ptr<srsgpu_context> ctx(new srsgpu_context());
   ctx->device = device;
   // Lifted shift tables: shifts[bg][position of Z][edge] = V(i_LS(Z), edge) mod Z (ldpc_luts_impl.cpp:4522).
   for (int bg = 1; bg <= 2; ++bg) {
@@ -386,22 +389,10 @@ int srsgpu_context_create(int device, srsgpu_context** out)
             static_cast<uint32_t>(A2) | (static_cast<uint32_t>(B2 & 0xffff) << 16);
       }
     }
-    if (hipMalloc(&ctx->d_pair_ab[bg - 1], ab.size() * sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(ctx->d_pair_ab[bg - 1], ab.data(), ab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMalloc(&ctx->d_pair_ab2[bg - 1], ab2.size() * sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(ctx->d_pair_ab2[bg - 1], ab2.data(), ab2.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
-            hipSuccess) {
-      srsgpu_context_destroy(ctx);
+    if (!ctx->d_pair_ab[bg - 1].upload(ab) || !ctx->d_pair_ab2[bg - 1].upload(ab2)) {
       return fail(SRSGPU_ERR_HIP, "failed to upload LDPC pair address tables");
     }
-    if (hipMalloc(&ctx->d_shifts[bg - 1], tab.size() * sizeof(uint16_t)) != hipSuccess ||
-        hipMemcpy(ctx->d_shifts[bg - 1], tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMalloc(&ctx->d_shifts32[bg - 1], tab32.size() * sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(ctx->d_shifts32[bg - 1], tab32.data(), tab32.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
-            hipSuccess) {
-      srsgpu_context_destroy(ctx);
+    if (!ctx->d_shifts[bg - 1].upload(tab) || !ctx->d_shifts32[bg - 1].upload(tab32)) {
       return fail(SRSGPU_ERR_HIP, "failed to upload LDPC shift tables");
     }
   }
@@ -409,19 +400,14 @@ int srsgpu_context_create(int device, srsgpu_context** out)
     ctx->core[bg - 1].resize(51);
     for (int p = 0; p < 51; ++p) {
       if (!build_core_plan(bg, kLiftingSizes[p], ctx->core[bg - 1][static_cast<size_t>(p)])) {
-        srsgpu_context_destroy(ctx);
         return fail(SRSGPU_ERR_INVALID_ARG, "cannot solve the LDPC core of BG%d Z=%d", bg, kLiftingSizes[p]);
       }
     }
-    if (hipMalloc(&ctx->d_core[bg - 1], 51 * sizeof(core_plan)) != hipSuccess ||
-        hipMemcpy(ctx->d_core[bg - 1], ctx->core[bg - 1].data(), 51 * sizeof(core_plan), hipMemcpyHostToDevice) !=
-            hipSuccess) {
-      srsgpu_context_destroy(ctx);
+    if (!ctx->d_core[bg - 1].upload(ctx->core[bg - 1])) {
       return fail(SRSGPU_ERR_HIP, "failed to upload the LDPC core plans");
     }
   }
-  if (hipMalloc(&ctx->d_crc_arena, CRC_ARENA_WORDS * sizeof(uint32_t)) != hipSuccess) {
-    srsgpu_context_destroy(ctx);
+  if (!ctx->d_crc_arena.alloc(CRC_ARENA_WORDS)) {
     return fail(SRSGPU_ERR_NO_MEMORY, "failed to allocate the CRC table arena");
   }
   {
@@ -450,14 +436,11 @@ int srsgpu_context_create(int device, srsgpu_context** out)
         }
       }
     }
-    if (hipMalloc(&ctx->d_crc_slice, tabs.size() * sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(ctx->d_crc_slice, tabs.data(), tabs.size() * sizeof(uint32_t), hipMemcpyHostToDevice) !=
-            hipSuccess) {
-      srsgpu_context_destroy(ctx);
+    if (!ctx->d_crc_slice.upload(tabs)) {
       return fail(SRSGPU_ERR_HIP, "failed to upload the slice-by-4 CRC tables");
     }
   }
-  *out = ctx;
+  *out = ctx.release();
   return SRSGPU_OK;
 }
 
@@ -527,39 +510,6 @@ void srsgpu_context_destroy(srsgpu_context* ctx)
     return;
   }
   (void)hipSetDevice(ctx->device);
-  for (auto* p : ctx->d_shifts) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
-  for (auto* p : ctx->d_shifts32) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
-  for (auto* p : ctx->d_pair_ab2) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
-  for (auto* p : ctx->d_pair_ab) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
-  for (auto* p : ctx->d_core) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
-  for (void* p : {static_cast<void*>(ctx->d_crc_arena), static_cast<void*>(ctx->d_crc_slice),
-                  static_cast<void*>(ctx->d_gold_x1),
-                  static_cast<void*>(ctx->d_gold_x2_jump), static_cast<void*>(ctx->d_gold_x2_lane),
-                  static_cast<void*>(ctx->d_ofdm_twiddles)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
   delete ctx;
 }
 
@@ -717,16 +667,14 @@ void pair_layout_for(const srsgpu_context* ctx, std::vector<dec_desc>& cbs, std:
   dms.swap(keep_dms);
 }
 
-int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, srsgpu_ldpc_decoder_plan** plan_out)
+int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch,
+                        plan_ptr<srsgpu_ldpc_decoder_plan>& plan_out)
 {
-  auto* plan = new srsgpu_ldpc_decoder_plan();
+  plan_ptr<srsgpu_ldpc_decoder_plan> plan(new srsgpu_ldpc_decoder_plan());
   plan->ctx  = ctx;
   plan->impl = impl;
-  auto upload = [&](void** dst, const void* src, size_t bytes) {
-    return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
   // Uploads a group's descriptors (dms: one per descriptor when fused, else empty; a descriptor with nof_llr = 0 is an
-  // empty slot of a two-codeblock workgroup) and adds it to the plan. The plan owns the group even when this fails.
+  // empty slot of a two-codeblock workgroup) and adds it to the plan, which then owns its buffers.
   auto add_group = [&](dec_group g, const std::vector<dec_desc>& descs, const std::vector<dm_desc>& dms) {
     for (size_t k = 0; k < descs.size(); ++k) {
       if (descs[k].nof_llr != 0u) {
@@ -734,15 +682,19 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
         plan->input_llrs += dms.empty() ? descs[k].nof_llr : static_cast<uint64_t>(dms[k].E) + dms[k].N;
       }
     }
-    const bool ok = upload(reinterpret_cast<void**>(&g.d_desc), descs.data(), descs.size() * sizeof(dec_desc)) &&
-                    (dms.empty() || upload(reinterpret_cast<void**>(&g.d_dm), dms.data(), dms.size() * sizeof(dm_desc)));
+    device_buffer<dec_desc> d_desc;
+    device_buffer<dm_desc>  d_dm;
+    if (!d_desc.upload(descs) || !d_dm.upload(dms)) {
+      return false;
+    }
+    g.d_desc = d_desc.get();
+    g.d_dm   = d_dm.get();
     plan->groups.push_back(g);
-    return ok;
+    plan->group_descs.push_back(std::move(d_desc));
+    plan->group_dms.push_back(std::move(d_dm));
+    return true;
   };
-  auto upload_failed = [&]() {
-    srsgpu_ldpc_decoder_plan_destroy(plan);
-    return fail(SRSGPU_ERR_HIP, "failed to upload decoder descriptors");
-  };
+  auto upload_failed = [&]() { return fail(SRSGPU_ERR_HIP, "failed to upload decoder descriptors"); };
   for (const auto& kv : batch.groups) {
     const bool            fused = std::get<3>(kv.first);
     std::vector<dec_desc> cbs   = kv.second;
@@ -789,7 +741,7 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
       return upload_failed();
     }
   }
-  *plan_out = plan;
+  plan_out = std::move(plan);
   return SRSGPU_OK;
 }
 
@@ -797,21 +749,21 @@ int upload_decoder_plan(srsgpu_context* ctx, int impl, const dec_batch& batch, s
 int execute_decoder_plan(const srsgpu_ldpc_decoder_plan* plan, dec_launch_args a)
 {
   a.mode         = plan->impl;
-  a.d_crc_tables = plan->ctx->d_crc_arena;
+  a.d_crc_tables = plan->ctx->d_crc_arena.get();
   for (const auto& g : plan->groups) {
     if (g.d_dm != nullptr && (a.d_cw_llrs == nullptr || (a.d_harq == nullptr && a.d_harq_cbs == nullptr))) {
       return fail(SRSGPU_ERR_INVALID_ARG, "fused decoder group without codeword LLRs / HARQ buffer");
     }
     if (g.pack == 2) {
-      launch_ldpc_decode_pairs(g, plan->ctx->d_pair_ab2[g.bg - 1], a);
+      launch_ldpc_decode_pairs(g, plan->ctx->d_pair_ab2[g.bg - 1].get(), a);
     } else if (g.packed) {
       // The edge-split kernel's CRC check takes a half's columns from its first lane: a half must be whole waves.
       if (g.split == 2 && g.threads % 128 != 0) {
         return fail(SRSGPU_ERR_INVALID_ARG, "edge-split decoder group of %d threads (not a multiple of 128)", g.threads);
       }
-      launch_ldpc_decode_pk(g, plan->ctx->d_pair_ab[g.bg - 1], a);
+      launch_ldpc_decode_pk(g, plan->ctx->d_pair_ab[g.bg - 1].get(), a);
     } else {
-      launch_ldpc_decode(g, plan->ctx->d_shifts32[g.bg - 1], a);
+      launch_ldpc_decode(g, plan->ctx->d_shifts32[g.bg - 1].get(), a);
     }
     HIP_TRY(hipGetLastError());
   }
@@ -919,24 +871,20 @@ int upload_pusch_cb_plan(srsgpu_context*             ctx,
                          int                         impl,
                          const dec_batch&            batch,
                          const std::vector<dm_desc>& dms,
-                         srsgpu_pusch_cb_plan**      plan_out)
+                         plan_ptr<srsgpu_pusch_cb_plan>& plan_out)
 {
-  auto* plan    = new srsgpu_pusch_cb_plan();
+  plan_ptr<srsgpu_pusch_cb_plan> plan(new srsgpu_pusch_cb_plan());
   plan->ctx     = ctx;
   plan->impl    = impl;
   plan->nof_cbs = static_cast<int>(dms.size());
-  int r         = upload_decoder_plan(ctx, impl, batch, &plan->dec);
+  int r         = upload_decoder_plan(ctx, impl, batch, plan->dec);
   if (r != SRSGPU_OK) {
-    delete plan;
     return r;
   }
-  if (!dms.empty() && (hipMalloc(&plan->d_dm, dms.size() * sizeof(dm_desc)) != hipSuccess ||
-                       hipMemcpy(plan->d_dm, dms.data(), dms.size() * sizeof(dm_desc), hipMemcpyHostToDevice) !=
-                           hipSuccess)) {
-    srsgpu_pusch_cb_plan_destroy(plan);
+  if (!plan->d_dm.upload(dms)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload rate dematcher descriptors");
   }
-  *plan_out = plan;
+  plan_out = std::move(plan);
   return SRSGPU_OK;
 }
 
@@ -948,7 +896,7 @@ int execute_pusch_cb_plan(const srsgpu_pusch_cb_plan* plan,
                           uint8_t*                    d_cb_crc_ok,
                           hipStream_t                 s)
 {
-  launch_rate_dematch(plan->impl, plan->d_dm, plan->nof_cbs, d_llrs, d_harq, d_cb_crc_ok, s);
+  launch_rate_dematch(plan->impl, plan->d_dm.get(), plan->nof_cbs, d_llrs, d_harq, d_cb_crc_ok, s);
   HIP_TRY(hipGetLastError());
   dec_launch_args a;
   a.d_llrs      = d_harq;
@@ -958,7 +906,7 @@ int execute_pusch_cb_plan(const srsgpu_pusch_cb_plan* plan,
   a.d_cb_crc_ok = d_cb_crc_ok;
   a.d_harq      = d_harq;
   a.stream      = s;
-  return execute_decoder_plan(plan->dec, a);
+  return execute_decoder_plan(plan->dec.get(), a);
 }
 
 } // namespace
@@ -991,9 +939,11 @@ int srsgpu_ldpc_decoder_plan_create(srsgpu_context*                   ctx,
       return r;
     }
   }
-  const int r = upload_decoder_plan(ctx, impl, batch, plan_out);
+  plan_ptr<srsgpu_ldpc_decoder_plan> plan;
+  const int                          r = upload_decoder_plan(ctx, impl, batch, plan);
   if (r == SRSGPU_OK) {
-    guard.commit((*plan_out)->crc_refs);
+    guard.commit(plan->crc_refs);
+    *plan_out = plan.release();
   }
   return r;
 }
@@ -1020,18 +970,7 @@ void srsgpu_ldpc_decoder_plan_destroy(srsgpu_ldpc_decoder_plan* plan)
   if (plan == nullptr) {
     return;
   }
-  if (!plan->crc_refs.empty()) {
-    std::lock_guard<std::mutex> lock(plan->ctx->mtx);
-    crc_release_locked(plan->ctx, plan->crc_refs);
-  }
-  for (auto& g : plan->groups) {
-    if (g.d_desc != nullptr) {
-      (void)hipFree(g.d_desc);
-    }
-    if (g.d_dm != nullptr) {
-      (void)hipFree(g.d_dm);
-    }
-  }
+  crc_release(plan->ctx, plan->crc_refs);
   delete plan;
 }
 
@@ -1089,9 +1028,11 @@ int srsgpu_pusch_cb_plan_create(srsgpu_context*               ctx,
       return r;
     }
   }
-  const int r = upload_pusch_cb_plan(ctx, impl, batch, dms, plan_out);
+  plan_ptr<srsgpu_pusch_cb_plan> plan;
+  const int                      r = upload_pusch_cb_plan(ctx, impl, batch, dms, plan);
   if (r == SRSGPU_OK) {
-    guard.commit((*plan_out)->crc_refs);
+    guard.commit(plan->crc_refs);
+    *plan_out = plan.release();
   }
   return r;
 }
@@ -1116,14 +1057,7 @@ void srsgpu_pusch_cb_plan_destroy(srsgpu_pusch_cb_plan* plan)
   if (plan == nullptr) {
     return;
   }
-  if (!plan->crc_refs.empty()) {
-    std::lock_guard<std::mutex> lock(plan->ctx->mtx);
-    crc_release_locked(plan->ctx, plan->crc_refs);
-  }
-  if (plan->d_dm != nullptr) {
-    (void)hipFree(plan->d_dm);
-  }
-  srsgpu_ldpc_decoder_plan_destroy(plan->dec);
+  crc_release(plan->ctx, plan->crc_refs);
   delete plan;
 }
 
@@ -1249,35 +1183,22 @@ int srsgpu_pdsch_encoder_plan_create(srsgpu_context*               ctx,
       slices.push_back({t, b, std::min(b + step, tbd[t].nbytes)});
     }
   }
-  auto* plan      = new srsgpu_pdsch_encoder_plan();
+  plan_ptr<srsgpu_pdsch_encoder_plan> plan(new srsgpu_pdsch_encoder_plan());
   plan->ctx       = ctx;
   plan->nof_tbs   = static_cast<int>(nof_tbs);
   plan->nof_slices = static_cast<int>(slices.size());
   plan->out_begin = nof_tbs ? out_begin : 0;
   plan->out_end   = out_end;
   plan->zero_output = zero_out;
-  bool ok         = true;
-  if (nof_tbs > 0) {
-    ok = hipMalloc(&plan->d_tb, tbd.size() * sizeof(tb_crc_desc)) == hipSuccess &&
-         hipMemcpy(plan->d_tb, tbd.data(), tbd.size() * sizeof(tb_crc_desc), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMalloc(&plan->d_tb_crc, tbd.size() * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc(&plan->d_slices, slices.size() * sizeof(tb_crc_slice)) == hipSuccess &&
-         hipMemcpy(plan->d_slices, slices.data(), slices.size() * sizeof(tb_crc_slice), hipMemcpyHostToDevice) ==
-             hipSuccess;
-  }
+  bool ok = plan->d_tb.upload(tbd) && plan->d_tb_crc.alloc(tbd.size()) && plan->d_slices.upload(slices);
   for (int b = 0; b < 2 && ok; ++b) {
     plan->count[b]    = static_cast<int>(encs[b].size());
     plan->count_pk[b] = static_cast<int>(encs_pk[b].size());
     plan->threads[b]  = ((maxz[b] + 63) / 64) * 64;
     encs[b].insert(encs[b].end(), encs_pk[b].begin(), encs_pk[b].end());
-    if (!encs[b].empty()) {
-      ok = hipMalloc(&plan->d_enc[b], encs[b].size() * sizeof(enc_desc)) == hipSuccess &&
-           hipMemcpy(plan->d_enc[b], encs[b].data(), encs[b].size() * sizeof(enc_desc), hipMemcpyHostToDevice) ==
-               hipSuccess;
-    }
+    ok = plan->d_enc[b].upload(encs[b]);
   }
   if (!ok) {
-    srsgpu_pdsch_encoder_plan_destroy(plan);
     return fail(SRSGPU_ERR_HIP, "failed to upload encoder descriptors");
   }
   plan->inline_tb_crc = plan->count[0] == 0 && plan->count[1] == 0 &&
@@ -1285,7 +1206,7 @@ int srsgpu_pdsch_encoder_plan_create(srsgpu_context*               ctx,
                           return t.table != NO_CRC_TABLE && t.nbytes <= TB_CRC_INLINE_MAX_BYTES;
                         });
   guard.commit(plan->crc_refs);
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -1311,22 +1232,24 @@ int srsgpu_pdsch_encoder_plan_execute(const srsgpu_pdsch_encoder_plan* plan,
     HIP_TRY(hipMemsetAsync(d_codewords + plan->out_begin, 0, plan->out_end - plan->out_begin, s));
   }
   if (!plan->inline_tb_crc && plan->nof_tbs > 0) {
-    HIP_TRY(hipMemsetAsync(plan->d_tb_crc, 0, static_cast<size_t>(plan->nof_tbs) * sizeof(uint32_t), s));
-    launch_tb_crc(plan->d_tb, plan->d_slices, plan->nof_slices, d_tbs, plan->d_tb_crc, plan->ctx->d_crc_arena, s);
+    HIP_TRY(hipMemsetAsync(plan->d_tb_crc.get(), 0, static_cast<size_t>(plan->nof_tbs) * sizeof(uint32_t), s));
+    launch_tb_crc(plan->d_tb.get(), plan->d_slices.get(), plan->nof_slices, d_tbs, plan->d_tb_crc.get(),
+                  plan->ctx->d_crc_arena.get(), s);
     HIP_TRY(hipGetLastError());
   }
   stage_timer::mark(ev, 1, s);
   for (int b = 0; b < 2; ++b) {
     auto* out = reinterpret_cast<uint32_t*>(d_codewords);
     if (plan->count_pk[b] > 0) {
-      launch_pdsch_encode_packed(b + 1, plan->d_enc[b] + plan->count[b], plan->count_pk[b], d_tbs, plan->d_tb_crc,
-                                 plan->inline_tb_crc ? plan->d_tb : nullptr, out, plan->ctx->d_shifts[b],
-                                 plan->ctx->d_core[b], plan->ctx->d_crc_arena, plan->ctx->d_crc_slice, s);
+      launch_pdsch_encode_packed(b + 1, plan->d_enc[b].get() + plan->count[b], plan->count_pk[b], d_tbs,
+                                 plan->d_tb_crc.get(), plan->inline_tb_crc ? plan->d_tb.get() : nullptr, out,
+                                 plan->ctx->d_shifts[b].get(), plan->ctx->d_core[b].get(), plan->ctx->d_crc_arena.get(),
+                                 plan->ctx->d_crc_slice.get(), s);
       HIP_TRY(hipGetLastError());
     }
     if (plan->count[b] > 0) {
-      launch_pdsch_encode(b + 1, plan->d_enc[b], plan->count[b], plan->threads[b], d_tbs, plan->d_tb_crc, out,
-                          plan->ctx->d_shifts[b], plan->ctx->d_core[b], plan->ctx->d_crc_arena, s);
+      launch_pdsch_encode(b + 1, plan->d_enc[b].get(), plan->count[b], plan->threads[b], d_tbs, plan->d_tb_crc.get(), out,
+                          plan->ctx->d_shifts[b].get(), plan->ctx->d_core[b].get(), plan->ctx->d_crc_arena.get(), s);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -1361,17 +1284,7 @@ void srsgpu_pdsch_encoder_plan_destroy(srsgpu_pdsch_encoder_plan* plan)
   if (plan == nullptr) {
     return;
   }
-  if (!plan->crc_refs.empty()) {
-    std::lock_guard<std::mutex> lock(plan->ctx->mtx);
-    crc_release_locked(plan->ctx, plan->crc_refs);
-  }
-  for (void* p : {static_cast<void*>(plan->d_tb), static_cast<void*>(plan->d_tb_crc), static_cast<void*>(plan->d_slices),
-                  static_cast<void*>(plan->d_enc[0]),
-                  static_cast<void*>(plan->d_enc[1])}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
-  }
+  crc_release(plan->ctx, plan->crc_refs);
   delete plan;
 }
 
@@ -1432,7 +1345,7 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
     d.tb_index     = t;
     d.crc_table    = (seg.C > 1) ? try_crc_table(ctx, SRSGPU_CRC24A, seg.tbs, guard.refs) : NO_CRC_TABLE;
   }
-  auto* plan    = new srsgpu_pusch_decoder_plan();
+  plan_ptr<srsgpu_pusch_decoder_plan> plan(new srsgpu_pusch_decoder_plan());
   plan->ctx     = ctx;
   plan->nof_tbs = static_cast<int>(nof_tbs);
   // 1 024 lanes when a TB is large (its CRC chain per lane shrinks 4x); one wave when every TB is a single small
@@ -1469,9 +1382,8 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
   // two-codeblock workgroups) none can take the already-decoded skip path, so every launch reaches a point where the
   // flag is known: the decoder writes both and the TB stage is not launched (srsgpu_pusch_decoder_plan_assemble
   // still runs it on request).
-  int r = upload_pusch_cb_plan(ctx, impl, batch, dms, &plan->cbs);
+  int r = upload_pusch_cb_plan(ctx, impl, batch, dms, plan->cbs);
   if (r != SRSGPU_OK) {
-    delete plan;
     return r;
   }
   // Decided from the launches the plan really holds: every group a fused one-codeblock packed launch.
@@ -1481,25 +1393,17 @@ int srsgpu_pusch_decoder_plan_create(srsgpu_context*               ctx,
                   std::all_of(groups.begin(), groups.end(), [](const dec_group& g) {
                     return g.packed && g.pack == 1 && g.d_dm != nullptr;
                   });
-  if (nof_tbs > 0 && (hipMalloc(&plan->d_tb, tbs.size() * sizeof(tb_dec_desc)) != hipSuccess ||
-                      hipMemcpy(plan->d_tb, tbs.data(), tbs.size() * sizeof(tb_dec_desc), hipMemcpyHostToDevice) !=
-                          hipSuccess)) {
-    srsgpu_pusch_decoder_plan_destroy(plan);
+  if (!plan->d_tb.upload(tbs)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload transport block descriptors");
   }
   if (!slices.empty()) {
-    if (hipMalloc(&plan->d_slices, slices.size() * sizeof(tb_slice)) != hipSuccess ||
-        hipMemcpy(plan->d_slices, slices.data(), slices.size() * sizeof(tb_slice), hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMalloc(&plan->d_tb_acc, 2 * tbs.size() * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(plan->d_tb_acc, 0, 2 * tbs.size() * sizeof(uint32_t)) != hipSuccess) {
-      srsgpu_pusch_decoder_plan_destroy(plan);
+    if (!plan->d_slices.upload(slices) || !plan->d_tb_acc.alloc_zeroed(2 * tbs.size())) {
       return fail(SRSGPU_ERR_HIP, "failed to upload transport block slices");
     }
     plan->nof_slices = static_cast<int>(slices.size());
   }
   guard.commit(plan->crc_refs);
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -1509,11 +1413,12 @@ void launch_plan_tb_stage(const srsgpu_pusch_decoder_plan* plan, uint8_t* d_cb_c
                           uint8_t* d_tbs, uint8_t* d_tb_crc_ok, hipStream_t s)
 {
   if (plan->nof_slices > 0) {
-    launch_pusch_tb_sliced(plan->d_tb, plan->d_slices, plan->nof_slices, d_cb_crc_ok, d_cb_msgs, d_tbs, d_tb_crc_ok,
-                           plan->ctx->d_crc_arena, plan->d_tb_acc, plan->d_tb_acc + plan->nof_tbs, s);
+    launch_pusch_tb_sliced(plan->d_tb.get(), plan->d_slices.get(), plan->nof_slices, d_cb_crc_ok, d_cb_msgs, d_tbs,
+                           d_tb_crc_ok, plan->ctx->d_crc_arena.get(), plan->d_tb_acc.get(),
+                           plan->d_tb_acc.get() + plan->nof_tbs, s);
   } else {
-    launch_pusch_tb(plan->d_tb, plan->nof_tbs, plan->tb_threads, d_cb_crc_ok, d_cb_msgs, d_tbs, d_tb_crc_ok,
-                    plan->ctx->d_crc_arena, s);
+    launch_pusch_tb(plan->d_tb.get(), plan->nof_tbs, plan->tb_threads, d_cb_crc_ok, d_cb_msgs, d_tbs, d_tb_crc_ok,
+                    plan->ctx->d_crc_arena.get(), s);
   }
 }
 } // namespace
@@ -1543,7 +1448,7 @@ int execute_pusch_decoder_plan(const srsgpu_pusch_decoder_plan* plan,
   auto* ev  = plan->timer.begin();
   auto* evd = plan->timer_dec.begin();
   stage_timer::mark(ev, 0, s);
-  launch_rate_dematch(plan->cbs->impl, plan->cbs->d_dm, plan->cbs->nof_cbs, d_llrs, d_harq, d_cb_crc_ok, s,
+  launch_rate_dematch(plan->cbs->impl, plan->cbs->d_dm.get(), plan->cbs->nof_cbs, d_llrs, d_harq, d_cb_crc_ok, s,
                       d_harq_cbs);
   HIP_TRY(hipGetLastError());
   stage_timer::mark(ev, 1, s);
@@ -1560,7 +1465,7 @@ int execute_pusch_decoder_plan(const srsgpu_pusch_decoder_plan* plan,
   a.d_tbs       = plan->fold_tb ? d_tbs : nullptr;
   a.d_tb_crc_ok = plan->fold_tb ? d_tb_crc_ok : nullptr;
   a.stream      = s;
-  int r         = execute_decoder_plan(plan->cbs->dec, a);
+  int r         = execute_decoder_plan(plan->cbs->dec.get(), a);
   if (r != SRSGPU_OK) {
     return r;
   }
@@ -1661,20 +1566,7 @@ void srsgpu_pusch_decoder_plan_destroy(srsgpu_pusch_decoder_plan* plan)
   if (plan == nullptr) {
     return;
   }
-  if (!plan->crc_refs.empty()) {
-    std::lock_guard<std::mutex> lock(plan->ctx->mtx);
-    crc_release_locked(plan->ctx, plan->crc_refs);
-  }
-  srsgpu_pusch_cb_plan_destroy(plan->cbs);
-  if (plan->d_tb != nullptr) {
-    (void)hipFree(plan->d_tb);
-  }
-  if (plan->d_slices != nullptr) {
-    (void)hipFree(plan->d_slices);
-  }
-  if (plan->d_tb_acc != nullptr) {
-    (void)hipFree(plan->d_tb_acc);
-  }
+  crc_release(plan->ctx, plan->crc_refs);
   delete plan;
 }
 
@@ -1699,5 +1591,12 @@ int srsgpu_debug_encoder_profile(uint64_t* dst, uint32_t n)
   return srsgpu::debug_read_encoder_profile(dst, n);
 }
 #endif
+
+/// Device allocations the library's plans and contexts hold at this moment (each owned by one device_buffer): what a
+/// create / destroy cycle must leave unchanged.
+int64_t srsgpu_debug_live_device_buffers(void)
+{
+  return g_live_device_buffers.load();
+}
 
 } // extern "C"

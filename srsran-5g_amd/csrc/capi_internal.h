@@ -7,7 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <atomic>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <mutex>
 #include <string>
@@ -54,31 +56,119 @@ struct crc_entry {
   uint64_t last_use = 0;
 };
 
+/// Device allocations owned by live device_buffer objects (srsgpu_debug_live_device_buffers).
+inline std::atomic<long> g_live_device_buffers{0};
+
+/// Owner of one hipMalloc allocation of T elements: what every plan and the context hold their device memory through.
+/// Move-only; null while it owns nothing, and left null by any call that fails.
+template <typename T>
+class device_buffer
+{
+public:
+  device_buffer() = default;
+  device_buffer(const device_buffer&)            = delete;
+  device_buffer& operator=(const device_buffer&) = delete;
+  device_buffer(device_buffer&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+  device_buffer& operator=(device_buffer&& o) noexcept
+  {
+    if (this != &o) {
+      release();
+      ptr   = o.ptr;
+      o.ptr = nullptr;
+    }
+    return *this;
+  }
+  ~device_buffer() { release(); }
+
+  /// Allocates n uninitialised elements (nothing, staying null, for n = 0).
+  bool alloc(size_t n)
+  {
+    release();
+    if (n == 0) {
+      return true;
+    }
+    if (hipMalloc(&ptr, n * sizeof(T)) != hipSuccess) {
+      ptr = nullptr;
+      return false;
+    }
+    ++g_live_device_buffers;
+    return true;
+  }
+  /// Allocates n elements and clears them.
+  bool alloc_zeroed(size_t n) { return alloc(n) && keep(n == 0 || hipMemset(ptr, 0, n * sizeof(T)) == hipSuccess); }
+  /// Allocates v.size() elements and copies v into them (blocking); an empty vector leaves the buffer null.
+  bool upload(const std::vector<T>& v)
+  {
+    return alloc(v.size()) &&
+           keep(v.empty() || hipMemcpy(ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
+  }
+  T*       get() const { return ptr; }
+  explicit operator bool() const { return ptr != nullptr; }
+
+private:
+  bool keep(bool ok)
+  {
+    if (!ok) {
+      release();
+    }
+    return ok;
+  }
+  void release()
+  {
+    if (ptr != nullptr) {
+      (void)hipFree(ptr);
+      --g_live_device_buffers;
+      ptr = nullptr;
+    }
+  }
+  T* ptr = nullptr;
+};
+
+/// Deleter of a plan held by a std::unique_ptr: the plan's C-ABI destroy function.
+struct plan_deleter {
+  void operator()(srsgpu_ldpc_decoder_plan* p) const { srsgpu_ldpc_decoder_plan_destroy(p); }
+  void operator()(srsgpu_pusch_cb_plan* p) const { srsgpu_pusch_cb_plan_destroy(p); }
+  void operator()(srsgpu_pusch_decoder_plan* p) const { srsgpu_pusch_decoder_plan_destroy(p); }
+  void operator()(srsgpu_pdsch_encoder_plan* p) const { srsgpu_pdsch_encoder_plan_destroy(p); }
+  void operator()(srsgpu_pdsch_modulator_plan* p) const { srsgpu_pdsch_modulator_plan_destroy(p); }
+  void operator()(srsgpu_pdsch_dmrs_plan* p) const { srsgpu_pdsch_dmrs_plan_destroy(p); }
+  void operator()(srsgpu_pdcch_plan* p) const { srsgpu_pdcch_plan_destroy(p); }
+  void operator()(srsgpu_ofdm_plan* p) const { srsgpu_ofdm_plan_destroy(p); }
+  void operator()(srsgpu_pusch_chest_plan* p) const { srsgpu_pusch_chest_plan_destroy(p); }
+  void operator()(srsgpu_pusch_demodulator_plan* p) const { srsgpu_pusch_demodulator_plan_destroy(p); }
+  void operator()(srsgpu_ulsch_demux_plan* p) const { srsgpu_ulsch_demux_plan_destroy(p); }
+  void operator()(srsgpu_uci_decoder_plan* p) const { srsgpu_uci_decoder_plan_destroy(p); }
+  void operator()(srsgpu_uci_polar_decoder_plan* p) const { srsgpu_uci_polar_decoder_plan_destroy(p); }
+};
+/// A plan under construction (released into *plan_out on success), or a nested plan owned by its parent.
+template <typename P>
+using plan_ptr = std::unique_ptr<P, plan_deleter>;
+
 } // namespace srsgpu
 
 struct srsgpu_context {
   int                                  device      = 0;
-  uint16_t*                            d_shifts[2] = {nullptr, nullptr};
-  uint32_t*                            d_shifts32[2] = {nullptr, nullptr};  ///< Same, one dword per shift (decoder).
+  srsgpu::device_buffer<uint16_t>      d_shifts[2];
+  srsgpu::device_buffer<uint32_t>      d_shifts32[2];  ///< Same, one dword per shift (decoder).
   /// Packed decoder address constants A | B << 16 per (Z position, edge), see ldpc_decoder_pk.hip (even Z only).
-  uint32_t*                            d_pair_ab[2] = {nullptr, nullptr};
-  uint32_t*                            d_pair_ab2[2] = {nullptr, nullptr};  ///< Same for the two-codeblock image.
-  srsgpu::core_plan*                   d_core[2]   = {nullptr, nullptr};
+  srsgpu::device_buffer<uint32_t>      d_pair_ab[2];
+  srsgpu::device_buffer<uint32_t>      d_pair_ab2[2];  ///< Same for the two-codeblock image.
+  srsgpu::device_buffer<srsgpu::core_plan> d_core[2];
   std::vector<srsgpu::core_plan>       core[2];
-  uint32_t*                            d_crc_arena = nullptr;
+  srsgpu::device_buffer<uint32_t>      d_crc_arena;
   /// Slice-by-4 byte tables (srsgpu::CRC_SLICE_WORDS per polynomial: CRC24A, CRC24B, CRC16), T_k[v] = v x^(order + 8 k)
   /// mod g, k = 0..3.
-  uint32_t*                            d_crc_slice = nullptr;
+  srsgpu::device_buffer<uint32_t>      d_crc_slice;
   std::map<srsgpu::crc_key, srsgpu::crc_entry> crc_tables;
   std::map<size_t, size_t>             crc_free = {{0, srsgpu::CRC_ARENA_WORDS}};  ///< Free blocks: offset -> words.
   uint64_t                             crc_clock = 0;
   /// Gold-sequence jump tables of the scrambler (built on first use, see srsgpu::gold_tables): x1 words, x2 chunk
   /// jumps M^(Nc + 2048 c) and x2 lane jumps M^(32 i), each matrix as 31 column words.
-  uint32_t*                            d_gold_x1      = nullptr;
-  uint32_t*                            d_gold_x2_jump = nullptr;
-  uint32_t*                            d_gold_x2_lane = nullptr;
+  srsgpu::device_buffer<uint32_t>      d_gold_x1;
+  srsgpu::device_buffer<uint32_t>      d_gold_x2_jump;
+  srsgpu::device_buffer<uint32_t>      d_gold_x2_lane;
   /// OFDM DFT twiddles exp(-j 2 pi m / OFDM_MAX_DFT) as (re, im) floats (built on first use).
-  float*                               d_ofdm_twiddles = nullptr;
+  srsgpu::device_buffer<float>         d_ofdm_twiddles;
   /// srsgpu_option values (srsgpu_context_set_option), read at plan creation.
   int opt_decoder_split         = -1;
   int opt_decoder_pairs         = 0;
@@ -100,6 +190,16 @@ inline void crc_release_locked(srsgpu_context* ctx, std::vector<crc_key>& refs)
     }
   }
   refs.clear();
+}
+
+/// The same from a plan's destroy function. A plan torn down inside its create function, which holds ctx->mtx, has
+/// committed no references yet and takes no lock.
+inline void crc_release(srsgpu_context* ctx, std::vector<crc_key>& refs)
+{
+  if (!refs.empty()) {
+    std::lock_guard<std::mutex> lock(ctx->mtx);
+    crc_release_locked(ctx, refs);
+  }
 }
 
 /// Releases the references taken during a plan creation unless they are committed to the plan (caller holds the lock
@@ -124,7 +224,7 @@ int build_gold_sequences(srsgpu_context*              ctx,
                          const std::vector<uint32_t>& c_inits,
                          const std::vector<uint32_t>& nwords,
                          const std::vector<uint32_t>& offsets,
-                         uint32_t**                   d_seq,
+                         device_buffer<uint32_t>&     d_seq,
                          const std::vector<uint32_t>* wstart = nullptr);
 
 /// Word offsets of the transmissions' sequences in a plan's sequence buffer (each padded by one word).

@@ -18,9 +18,9 @@ struct srsgpu_ofdm_plan {
   uint32_t              nsc        = 0;
   uint32_t              window_off = 0;
   uint32_t              nof_ports  = 0;
-  ofdm_job*             d_jobs     = nullptr;
+  device_buffer<ofdm_job> d_jobs;
   int                   nof_jobs   = 0;
-  float*                d_scratch  = nullptr;  ///< Split sizes: one N-point complex row per job.
+  device_buffer<float>  d_scratch;  ///< Split sizes: one N-point complex row per job.
   std::vector<uint64_t> offsets;     ///< Sample offset of (grid, port); one extra entry = total.
   uint64_t              grid_words = 0;  ///< uint32 words of the plan's grids (all grids, ports and symbols).
 };
@@ -45,7 +45,7 @@ uint32_t cp_samples(uint32_t mu, uint32_t N, bool extended, uint32_t symbol)
 
 int ensure_twiddles(srsgpu_context* ctx)
 {
-  if (ctx->d_ofdm_twiddles != nullptr) {
+  if (ctx->d_ofdm_twiddles) {
     return SRSGPU_OK;
   }
   std::vector<float> tw(2 * OFDM_MAX_DFT);
@@ -54,15 +54,11 @@ int ensure_twiddles(srsgpu_context* ctx)
     tw[2 * m]      = static_cast<float>(std::cos(a));
     tw[2 * m + 1]  = static_cast<float>(std::sin(a));
   }
-  float* d = nullptr;
-  if (hipMalloc(&d, tw.size() * sizeof(float)) != hipSuccess ||
-      hipMemcpy(d, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    if (d != nullptr) {
-      (void)hipFree(d);
-    }
+  device_buffer<float> d;
+  if (!d.upload(tw)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload the DFT twiddle table");
   }
-  ctx->d_ofdm_twiddles = d;
+  ctx->d_ofdm_twiddles = std::move(d);
   return SRSGPU_OK;
 }
 
@@ -137,7 +133,7 @@ int plan_create(srsgpu_context*           ctx,
   if (r != SRSGPU_OK) {
     return r;
   }
-  auto* plan       = new srsgpu_ofdm_plan();
+  plan_ptr<srsgpu_ofdm_plan> plan(new srsgpu_ofdm_plan());
   plan->ctx        = ctx;
   plan->inverse    = inverse;
   plan->dft_size   = N;
@@ -148,7 +144,6 @@ int plan_create(srsgpu_context*           ctx,
   uint64_t              pos = 0;
   for (uint32_t g = 0; g < nof_grids; ++g) {
     if (slot_index[g] >= nslot) {
-      delete plan;
       return fail(SRSGPU_ERR_INVALID_ARG, "grid %u: slot index %u exceeds the %u slots per subframe", g, slot_index[g],
                   nslot);
     }
@@ -172,23 +167,17 @@ int plan_create(srsgpu_context*           ctx,
   plan->offsets.push_back(pos);
   plan->grid_words = static_cast<uint64_t>(nof_grids) * nof_ports * nof_symbols * nsc;
   if (pos >= (1ull << 32) || static_cast<uint64_t>(nof_grids) * nof_ports * nof_symbols * nsc >= (1ull << 32)) {
-    delete plan;
     return fail(SRSGPU_ERR_INVALID_ARG, "batch too large for 32-bit offsets");
   }
   plan->nof_jobs = static_cast<int>(jobs.size());
-  if (!jobs.empty() && (hipMalloc(&plan->d_jobs, jobs.size() * sizeof(ofdm_job)) != hipSuccess ||
-                        hipMemcpy(plan->d_jobs, jobs.data(), jobs.size() * sizeof(ofdm_job), hipMemcpyHostToDevice) !=
-                            hipSuccess)) {
-    srsgpu_ofdm_plan_destroy(plan);
+  if (!plan->d_jobs.upload(jobs)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload OFDM jobs");
   }
-  if (!jobs.empty() && ofdm_split_factor(N) != 0 &&
-      hipMalloc(&plan->d_scratch, jobs.size() * static_cast<size_t>(N) * 2 * sizeof(float)) != hipSuccess) {
-    srsgpu_ofdm_plan_destroy(plan);
+  if (ofdm_split_factor(N) != 0 && !plan->d_scratch.alloc(jobs.size() * static_cast<size_t>(N) * 2)) {
     return fail(SRSGPU_ERR_HIP, "failed to allocate the split-transform scratch (%zu MB)",
                 jobs.size() * static_cast<size_t>(N) * 8 / (1u << 20));
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -255,7 +244,7 @@ int srsgpu_ofdm_plan_concat(srsgpu_context*                ctx,
   std::vector<ofdm_job> jobs;
   uint64_t              samples = 0;
   uint64_t              words   = 0;
-  auto*                 plan    = new srsgpu_ofdm_plan();
+  plan_ptr<srsgpu_ofdm_plan> plan(new srsgpu_ofdm_plan());
   plan->ctx        = ctx;
   plan->inverse    = first->inverse;
   plan->dft_size   = first->dft_size;
@@ -267,7 +256,6 @@ int srsgpu_ofdm_plan_concat(srsgpu_context*                ctx,
     // One kernel runs every job: the members must agree on what the launch takes from the plan.
     if (m == nullptr || m->ctx != ctx || m->inverse != first->inverse || m->dft_size != first->dft_size ||
         m->nsc != first->nsc || m->window_off != first->window_off || m->nof_ports != first->nof_ports) {
-      delete plan;
       return fail(SRSGPU_ERR_INVALID_ARG,
                   "member plan %u differs from the first in context, direction, DFT size, bandwidth, window offset or "
                   "ports",
@@ -275,9 +263,8 @@ int srsgpu_ofdm_plan_concat(srsgpu_context*                ctx,
     }
     const size_t base = jobs.size();
     jobs.resize(base + m->nof_jobs);
-    if (m->nof_jobs > 0 && hipMemcpy(jobs.data() + base, m->d_jobs, m->nof_jobs * sizeof(ofdm_job),
+    if (m->nof_jobs > 0 && hipMemcpy(jobs.data() + base, m->d_jobs.get(), m->nof_jobs * sizeof(ofdm_job),
                                      hipMemcpyDeviceToHost) != hipSuccess) {
-      delete plan;
       return fail(SRSGPU_ERR_HIP, "failed to read member plan %u's jobs", i);
     }
     for (size_t j = base; j != jobs.size(); ++j) {
@@ -290,26 +277,20 @@ int srsgpu_ofdm_plan_concat(srsgpu_context*                ctx,
     samples += m->offsets.empty() ? 0 : m->offsets.back();
     words += m->grid_words;
     if (samples >= (1ull << 32) || words >= (1ull << 32)) {
-      delete plan;
       return fail(SRSGPU_ERR_INVALID_ARG, "batch too large for 32-bit offsets");
     }
   }
   plan->offsets.push_back(samples);
   plan->grid_words = words;
   plan->nof_jobs   = static_cast<int>(jobs.size());
-  if (!jobs.empty() && (hipMalloc(&plan->d_jobs, jobs.size() * sizeof(ofdm_job)) != hipSuccess ||
-                        hipMemcpy(plan->d_jobs, jobs.data(), jobs.size() * sizeof(ofdm_job), hipMemcpyHostToDevice) !=
-                            hipSuccess)) {
-    srsgpu_ofdm_plan_destroy(plan);
+  if (!plan->d_jobs.upload(jobs)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload OFDM jobs");
   }
-  if (!jobs.empty() && ofdm_split_factor(plan->dft_size) != 0 &&
-      hipMalloc(&plan->d_scratch, jobs.size() * static_cast<size_t>(plan->dft_size) * 2 * sizeof(float)) !=
-          hipSuccess) {
-    srsgpu_ofdm_plan_destroy(plan);
+  if (ofdm_split_factor(plan->dft_size) != 0 &&
+      !plan->d_scratch.alloc(jobs.size() * static_cast<size_t>(plan->dft_size) * 2)) {
     return fail(SRSGPU_ERR_HIP, "failed to allocate the split-transform scratch");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -328,7 +309,7 @@ int srsgpu_ofdm_plan_get_jobs(const srsgpu_ofdm_plan* plan, srsgpu_ofdm_job* job
   if (n > 0) {
     std::lock_guard<std::mutex> lock(plan->ctx->mtx);
     HIP_TRY(hipSetDevice(plan->ctx->device));
-    HIP_TRY(hipMemcpy(jobs, plan->d_jobs, n * sizeof(ofdm_job), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(jobs, plan->d_jobs.get(), n * sizeof(ofdm_job), hipMemcpyDeviceToHost));
   }
   return SRSGPU_OK;
 }
@@ -351,12 +332,12 @@ int srsgpu_ofdm_jobs_execute(const srsgpu_ofdm_plan* plan,
   }
   const auto* jobs = reinterpret_cast<const ofdm_job*>(d_jobs);
   if (plan->inverse) {
-    launch_ofdm(true, plan->dft_size, jobs, static_cast<int>(nof_jobs), plan->nsc, 0, plan->ctx->d_ofdm_twiddles,
+    launch_ofdm(true, plan->dft_size, jobs, static_cast<int>(nof_jobs), plan->nsc, 0, plan->ctx->d_ofdm_twiddles.get(),
                 static_cast<const uint32_t*>(d_in), nullptr, nullptr, static_cast<float*>(d_out), nullptr,
                 static_cast<hipStream_t>(stream));
   } else {
     launch_ofdm(false, plan->dft_size, jobs, static_cast<int>(nof_jobs), plan->nsc, plan->window_off,
-                plan->ctx->d_ofdm_twiddles, nullptr, static_cast<uint32_t*>(d_out), static_cast<const float*>(d_in),
+                plan->ctx->d_ofdm_twiddles.get(), nullptr, static_cast<uint32_t*>(d_out), static_cast<const float*>(d_in),
                 nullptr, nullptr, static_cast<hipStream_t>(stream));
   }
   HIP_TRY(hipGetLastError());
@@ -375,7 +356,7 @@ int srsgpu_ofdm_jobs_execute_direct(const srsgpu_ofdm_plan*       plan,
     return fail(SRSGPU_ERR_INVALID_ARG, "job lists do not run the split DFT sizes (%u points)", plan->dft_size);
   }
   if (!launch_ofdm_direct(plan->inverse, plan->dft_size, d_jobs, static_cast<int>(nof_jobs), plan->nsc,
-                          plan->inverse ? 0u : plan->window_off, plan->ctx->d_ofdm_twiddles,
+                          plan->inverse ? 0u : plan->window_off, plan->ctx->d_ofdm_twiddles.get(),
                           static_cast<hipStream_t>(stream))) {
     return fail(SRSGPU_ERR_INVALID_ARG, "unsupported DFT size %u", plan->dft_size);
   }
@@ -410,8 +391,8 @@ int srsgpu_ofdm_modulator_plan_execute(const srsgpu_ofdm_plan* plan,
   if (plan == nullptr || d_grids == nullptr || d_samples == nullptr || !plan->inverse) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument or not a modulator plan");
   }
-  launch_ofdm(true, plan->dft_size, plan->d_jobs, plan->nof_jobs, plan->nsc, 0, plan->ctx->d_ofdm_twiddles, d_grids,
-              nullptr, nullptr, d_samples, plan->d_scratch, static_cast<hipStream_t>(stream));
+  launch_ofdm(true, plan->dft_size, plan->d_jobs.get(), plan->nof_jobs, plan->nsc, 0, plan->ctx->d_ofdm_twiddles.get(), d_grids,
+              nullptr, nullptr, d_samples, plan->d_scratch.get(), static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -428,8 +409,8 @@ int srsgpu_ofdm_modulator_plan_execute_twin(const srsgpu_ofdm_plan* plan,
   if (ofdm_split_factor(plan->dft_size) != 0) {
     return fail(SRSGPU_ERR_INVALID_ARG, "no twin grid for the split DFT size %u", plan->dft_size);
   }
-  launch_ofdm(true, plan->dft_size, plan->d_jobs, plan->nof_jobs, plan->nsc, 0, plan->ctx->d_ofdm_twiddles, d_grids,
-              nullptr, nullptr, d_samples, plan->d_scratch, static_cast<hipStream_t>(stream), d_twin);
+  launch_ofdm(true, plan->dft_size, plan->d_jobs.get(), plan->nof_jobs, plan->nsc, 0, plan->ctx->d_ofdm_twiddles.get(), d_grids,
+              nullptr, nullptr, d_samples, plan->d_scratch.get(), static_cast<hipStream_t>(stream), d_twin);
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -442,8 +423,8 @@ int srsgpu_ofdm_demodulator_plan_execute(const srsgpu_ofdm_plan* plan,
   if (plan == nullptr || d_grids == nullptr || d_samples == nullptr || plan->inverse) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument or not a demodulator plan");
   }
-  launch_ofdm(false, plan->dft_size, plan->d_jobs, plan->nof_jobs, plan->nsc, plan->window_off,
-              plan->ctx->d_ofdm_twiddles, nullptr, d_grids, d_samples, nullptr, plan->d_scratch,
+  launch_ofdm(false, plan->dft_size, plan->d_jobs.get(), plan->nof_jobs, plan->nsc, plan->window_off,
+              plan->ctx->d_ofdm_twiddles.get(), nullptr, d_grids, d_samples, nullptr, plan->d_scratch.get(),
               static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
@@ -453,12 +434,6 @@ void srsgpu_ofdm_plan_destroy(srsgpu_ofdm_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  if (plan->d_jobs != nullptr) {
-    (void)hipFree(plan->d_jobs);
-  }
-  if (plan->d_scratch != nullptr) {
-    (void)hipFree(plan->d_scratch);
   }
   delete plan;
 }

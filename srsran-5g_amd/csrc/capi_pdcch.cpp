@@ -17,12 +17,12 @@ static_assert(sizeof(srsgpu_pdcch_config) == 128, "srsgpu_pdcch_config layout (m
 
 struct srsgpu_pdcch_plan {
   srsgpu_context*  ctx           = nullptr;
-  pdcch_desc*      d_descs       = nullptr;
-  pdcch_code_desc* d_codes       = nullptr;
-  uint8_t*         d_u_source    = nullptr;
-  uint32_t*        d_gather      = nullptr;
-  uint16_t*        d_prbs        = nullptr;
-  uint32_t*        d_crc_weights = nullptr;
+  device_buffer<pdcch_desc>      d_descs;
+  device_buffer<pdcch_code_desc> d_codes;
+  device_buffer<uint8_t>         d_u_source;
+  device_buffer<uint32_t>        d_gather;
+  device_buffer<uint16_t>        d_prbs;
+  device_buffer<uint32_t>        d_crc_weights;
   uint32_t         nof_dcis      = 0;
   uint64_t         payload_bytes = 0;  ///< The payload buffer must hold at least this many bytes.
 };
@@ -30,14 +30,6 @@ struct srsgpu_pdcch_plan {
 namespace {
 
 constexpr uint32_t CRC24C_POLY = 0x1b2b117;
-
-template <typename T>
-bool upload(T** d_ptr, const std::vector<T>& host)
-{
-  const size_t bytes = std::max<size_t>(host.size(), 1) * sizeof(T);
-  return hipMalloc(d_ptr, bytes) == hipSuccess &&
-         (host.empty() || hipMemcpy(*d_ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
-}
 
 /// x^(24 + j) mod g_CRC24C (crc_calculator_generic_impl.cpp:40: 0x1b2b117), j = 0..PDCCH_CRC_WEIGHTS-1.
 std::vector<uint32_t> crc24c_weights()
@@ -193,20 +185,17 @@ int srsgpu_pdcch_plan_create(srsgpu_context*            ctx,
   if (int r = ensure_gold_tables(ctx)) {
     return r;
   }
-  auto* plan          = new srsgpu_pdcch_plan();
+  plan_ptr<srsgpu_pdcch_plan> plan(new srsgpu_pdcch_plan());
   plan->ctx           = ctx;
   plan->nof_dcis      = nof_dcis;
   plan->payload_bytes = payload_bytes;
-  if (nof_dcis > 0) {
-    const bool ok = upload(&plan->d_descs, descs) && upload(&plan->d_codes, codes) && upload(&plan->d_u_source, u_source) &&
-                    upload(&plan->d_gather, gather) && upload(&plan->d_prbs, prb_table) &&
-                    upload(&plan->d_crc_weights, crc_w);
-    if (!ok) {
-      srsgpu_pdcch_plan_destroy(plan);
-      return fail(SRSGPU_ERR_HIP, "failed to upload the PDCCH tables");
-    }
+  // With a DCI there is a code with its tables and at least one PRB: none of the six tables is empty then.
+  if (nof_dcis > 0 && (!plan->d_descs.upload(descs) || !plan->d_codes.upload(codes) ||
+                       !plan->d_u_source.upload(u_source) || !plan->d_gather.upload(gather) ||
+                       !plan->d_prbs.upload(prb_table) || !plan->d_crc_weights.upload(crc_w))) {
+    return fail(SRSGPU_ERR_HIP, "failed to upload the PDCCH tables");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -223,9 +212,9 @@ int srsgpu_pdcch_plan_execute(const srsgpu_pdcch_plan* plan,
     return fail(SRSGPU_ERR_INVALID_ARG, "the payload buffer holds %llu bytes, the plan's DCIs read %llu",
                 static_cast<unsigned long long>(payload_bytes), static_cast<unsigned long long>(plan->payload_bytes));
   }
-  launch_pdcch(plan->d_descs, plan->nof_dcis, plan->d_codes, plan->d_u_source, plan->d_gather, plan->d_prbs,
-               plan->d_crc_weights, d_payloads, d_grids, plan->ctx->d_gold_x1, plan->ctx->d_gold_x2_jump,
-               plan->ctx->d_gold_x2_lane, static_cast<hipStream_t>(stream));
+  launch_pdcch(plan->d_descs.get(), plan->nof_dcis, plan->d_codes.get(), plan->d_u_source.get(), plan->d_gather.get(),
+               plan->d_prbs.get(), plan->d_crc_weights.get(), d_payloads, d_grids, plan->ctx->d_gold_x1.get(),
+               plan->ctx->d_gold_x2_jump.get(), plan->ctx->d_gold_x2_lane.get(), static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -234,13 +223,6 @@ void srsgpu_pdcch_plan_destroy(srsgpu_pdcch_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  for (void* p : {static_cast<void*>(plan->d_descs), static_cast<void*>(plan->d_codes), static_cast<void*>(plan->d_u_source),
-                  static_cast<void*>(plan->d_gather), static_cast<void*>(plan->d_prbs),
-                  static_cast<void*>(plan->d_crc_weights)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
   }
   delete plan;
 }

@@ -14,19 +14,19 @@ static_assert(sizeof(srsgpu_pdsch_dmrs_config) == 152, "srsgpu_pdsch_dmrs_config
 
 struct srsgpu_pdsch_dmrs_plan {
   srsgpu_context* ctx      = nullptr;
-  dmrs_job*       d_jobs   = nullptr;
-  uint32_t*       d_seq    = nullptr;  ///< DM-RS sequence words of every job (plan lifetime).
+  device_buffer<dmrs_job> d_jobs;
+  device_buffer<uint32_t> d_seq;  ///< DM-RS sequence words of every job (plan lifetime).
   int             nof_jobs = 0;
   int             max_pilots = 0;  ///< Largest job (workgroups per job of the launch).
 };
 
 struct srsgpu_pdsch_modulator_plan {
   srsgpu_context* ctx        = nullptr;
-  mod_desc*       d_desc     = nullptr;
-  uint16_t*       d_sc_map   = nullptr;  ///< RE -> grid subcarrier maps of the general allocations.
-  float*          d_prg_w    = nullptr;  ///< Per-PRG weights [prg][port 4][layer 4][2] (amplitude folded in).
-  mod_chunk*      d_chunks   = nullptr;
-  uint32_t*       d_seq      = nullptr;  ///< Scrambling sequences of the transmissions (plan lifetime).
+  device_buffer<mod_desc>  d_desc;
+  device_buffer<uint16_t>  d_sc_map;  ///< RE -> grid subcarrier maps of the general allocations.
+  device_buffer<float>     d_prg_w;   ///< Per-PRG weights [prg][port 4][layer 4][2] (amplitude folded in).
+  device_buffer<mod_chunk> d_chunks;
+  device_buffer<uint32_t>  d_seq;  ///< Scrambling sequences of the transmissions (plan lifetime).
   int             nof_chunks = 0;
 };
 
@@ -74,10 +74,9 @@ int srsgpu::build_gold_sequences(srsgpu_context*              ctx,
                                  const std::vector<uint32_t>& c_inits,
                                  const std::vector<uint32_t>& nwords,
                                  const std::vector<uint32_t>& offsets,
-                                 uint32_t**                   d_seq,
+                                 device_buffer<uint32_t>&     d_seq,
                                  const std::vector<uint32_t>* wstart)
 {
-  *d_seq = nullptr;
   if (c_inits.empty()) {
     return SRSGPU_OK;
   }
@@ -88,38 +87,31 @@ int srsgpu::build_gold_sequences(srsgpu_context*              ctx,
     total = std::max(total, static_cast<size_t>(offsets[t]) + nwords[t] + 1u);
     maxw  = std::max(maxw, nwords[t]);
   }
-  uint32_t* d_small = nullptr;  // c_inits | offsets | nwords | wstart
-  bool      ok      = hipMalloc(reinterpret_cast<void**>(d_seq), total * 4) == hipSuccess &&
-               hipMemset(*d_seq, 0, total * 4) == hipSuccess &&
-               hipMalloc(reinterpret_cast<void**>(&d_small), 4 * n * 4) == hipSuccess &&
-               hipMemcpy(d_small, c_inits.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-               hipMemcpy(d_small + n, offsets.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-               hipMemcpy(d_small + 2 * n, nwords.data(), n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-               (wstart == nullptr ||
-                hipMemcpy(d_small + 3 * n, wstart->data(), n * 4, hipMemcpyHostToDevice) == hipSuccess);
+  std::vector<uint32_t> small(c_inits);  // c_inits | offsets | nwords | wstart
+  small.insert(small.end(), offsets.begin(), offsets.begin() + n);
+  small.insert(small.end(), nwords.begin(), nwords.begin() + n);
+  if (wstart != nullptr) {
+    small.insert(small.end(), wstart->begin(), wstart->begin() + n);
+  }
+  device_buffer<uint32_t> seq, d_small;
+  bool                    ok = seq.alloc_zeroed(total) && d_small.upload(small);
   if (ok) {
-    launch_gold_fill(d_small, d_small + n, d_small + 2 * n, wstart != nullptr ? d_small + 3 * n : nullptr,
-                     static_cast<int>(n), maxw, *d_seq, ctx->d_gold_x1, ctx->d_gold_x2_jump, ctx->d_gold_x2_lane,
-                     nullptr);
+    const uint32_t* p = d_small.get();
+    launch_gold_fill(p, p + n, p + 2 * n, wstart != nullptr ? p + 3 * n : nullptr, static_cast<int>(n), maxw,
+                     seq.get(), ctx->d_gold_x1.get(), ctx->d_gold_x2_jump.get(), ctx->d_gold_x2_lane.get(), nullptr);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
   }
-  if (d_small != nullptr) {
-    (void)hipFree(d_small);
-  }
   if (!ok) {
-    if (*d_seq != nullptr) {
-      (void)hipFree(*d_seq);
-      *d_seq = nullptr;
-    }
     return fail(SRSGPU_ERR_HIP, "failed to build the scrambling sequences");
   }
+  d_seq = std::move(seq);
   return SRSGPU_OK;
 }
 
 /// Builds and uploads the scrambler's Gold-sequence tables into the context (once; caller holds ctx->mtx).
 int srsgpu::ensure_gold_tables(srsgpu_context* ctx)
 {
-  if (ctx->d_gold_x1 != nullptr) {
+  if (ctx->d_gold_x1) {
     return SRSGPU_OK;
   }
   // x1 (initial state x1(0) = 1): words of x1(Nc + 32 w + k), bit k.
@@ -167,22 +159,13 @@ int srsgpu::ensure_gold_tables(srsgpu_context* ctx)
       cur[j] = gf2_apply(m2048, cur[j]);
     }
   }
-  uint32_t *d_x1 = nullptr, *d_jump = nullptr, *d_lane = nullptr;
-  if (hipMalloc(&d_x1, x1.size() * 4) != hipSuccess || hipMalloc(&d_jump, jump.size() * 4) != hipSuccess ||
-      hipMalloc(&d_lane, lane.size() * 4) != hipSuccess ||
-      hipMemcpy(d_x1, x1.data(), x1.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_jump, jump.data(), jump.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_lane, lane.data(), lane.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    for (uint32_t* p : {d_x1, d_jump, d_lane}) {
-      if (p != nullptr) {
-        (void)hipFree(p);
-      }
-    }
+  device_buffer<uint32_t> d_x1, d_jump, d_lane;
+  if (!d_x1.upload(x1) || !d_jump.upload(jump) || !d_lane.upload(lane)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload the Gold sequence tables");
   }
-  ctx->d_gold_x1      = d_x1;
-  ctx->d_gold_x2_jump = d_jump;
-  ctx->d_gold_x2_lane = d_lane;
+  ctx->d_gold_x1      = std::move(d_x1);
+  ctx->d_gold_x2_jump = std::move(d_jump);
+  ctx->d_gold_x2_lane = std::move(d_lane);
   return SRSGPU_OK;
 }
 
@@ -397,35 +380,19 @@ int srsgpu_pdsch_modulator_plan_create_ex(srsgpu_context*                ctx,
   for (size_t t = 0; t < descs.size(); ++t) {
     descs[t].seq_word_offset = seq_off[t];
   }
-  auto* plan       = new srsgpu_pdsch_modulator_plan();
+  plan_ptr<srsgpu_pdsch_modulator_plan> plan(new srsgpu_pdsch_modulator_plan());
   plan->ctx        = ctx;
   plan->nof_chunks = static_cast<int>(chunks.size());
-  bool ok          = true;
   if (!chunks.empty()) {
-    if (build_gold_sequences(ctx, c_inits, nwords, seq_off, &plan->d_seq) != SRSGPU_OK) {
-      srsgpu_pdsch_modulator_plan_destroy(plan);
+    if (build_gold_sequences(ctx, c_inits, nwords, seq_off, plan->d_seq) != SRSGPU_OK) {
       return SRSGPU_ERR_HIP;
     }
-    ok = hipMalloc(&plan->d_desc, descs.size() * sizeof(mod_desc)) == hipSuccess &&
-         hipMemcpy(plan->d_desc, descs.data(), descs.size() * sizeof(mod_desc), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMalloc(&plan->d_chunks, chunks.size() * sizeof(mod_chunk)) == hipSuccess &&
-         hipMemcpy(plan->d_chunks, chunks.data(), chunks.size() * sizeof(mod_chunk), hipMemcpyHostToDevice) ==
-             hipSuccess;
-    if (ok && !sc_map.empty()) {
-      ok = hipMalloc(&plan->d_sc_map, sc_map.size() * sizeof(uint16_t)) == hipSuccess &&
-           hipMemcpy(plan->d_sc_map, sc_map.data(), sc_map.size() * sizeof(uint16_t), hipMemcpyHostToDevice) ==
-               hipSuccess;
-    }
-    if (ok && !prg_w.empty()) {
-      ok = hipMalloc(&plan->d_prg_w, prg_w.size() * sizeof(float)) == hipSuccess &&
-           hipMemcpy(plan->d_prg_w, prg_w.data(), prg_w.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (!plan->d_desc.upload(descs) || !plan->d_chunks.upload(chunks) || !plan->d_sc_map.upload(sc_map) ||
+        !plan->d_prg_w.upload(prg_w)) {
+      return fail(SRSGPU_ERR_HIP, "failed to upload modulator descriptors");
     }
   }
-  if (!ok) {
-    srsgpu_pdsch_modulator_plan_destroy(plan);
-    return fail(SRSGPU_ERR_HIP, "failed to upload modulator descriptors");
-  }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -437,8 +404,8 @@ int srsgpu_pdsch_modulator_plan_execute(const srsgpu_pdsch_modulator_plan* plan,
   if (plan == nullptr || d_codewords == nullptr || d_grids == nullptr) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
-  launch_pdsch_modulate(plan->d_desc, plan->d_sc_map, plan->d_prg_w, plan->d_chunks, plan->nof_chunks,
-                        reinterpret_cast<const uint32_t*>(d_codewords), d_grids, plan->d_seq,
+  launch_pdsch_modulate(plan->d_desc.get(), plan->d_sc_map.get(), plan->d_prg_w.get(), plan->d_chunks.get(),
+                        plan->nof_chunks, reinterpret_cast<const uint32_t*>(d_codewords), d_grids, plan->d_seq.get(),
                         static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
@@ -448,13 +415,6 @@ void srsgpu_pdsch_modulator_plan_destroy(srsgpu_pdsch_modulator_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  for (void* p : {static_cast<void*>(plan->d_desc), static_cast<void*>(plan->d_chunks),
-                  static_cast<void*>(plan->d_seq), static_cast<void*>(plan->d_sc_map),
-                  static_cast<void*>(plan->d_prg_w)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
   }
   delete plan;
 }
@@ -553,7 +513,7 @@ int srsgpu_pdsch_dmrs_plan_create_ex(srsgpu_context*                 ctx,
   if (r != SRSGPU_OK) {
     return r;
   }
-  auto* plan     = new srsgpu_pdsch_dmrs_plan();
+  plan_ptr<srsgpu_pdsch_dmrs_plan> plan(new srsgpu_pdsch_dmrs_plan());
   plan->ctx      = ctx;
   plan->nof_jobs = static_cast<int>(jobs.size());
   for (const dmrs_job& j : jobs) {
@@ -572,17 +532,13 @@ int srsgpu_pdsch_dmrs_plan_create_ex(srsgpu_context*                 ctx,
     wstart.push_back(n0 >> 5);
     base += nw;
   }
-  if (build_gold_sequences(ctx, c_inits, nwords, offsets, &plan->d_seq, &wstart) != SRSGPU_OK) {
-    srsgpu_pdsch_dmrs_plan_destroy(plan);
+  if (build_gold_sequences(ctx, c_inits, nwords, offsets, plan->d_seq, &wstart) != SRSGPU_OK) {
     return SRSGPU_ERR_HIP;
   }
-  if (!jobs.empty() && (hipMalloc(&plan->d_jobs, jobs.size() * sizeof(dmrs_job)) != hipSuccess ||
-                        hipMemcpy(plan->d_jobs, jobs.data(), jobs.size() * sizeof(dmrs_job), hipMemcpyHostToDevice) !=
-                            hipSuccess)) {
-    srsgpu_pdsch_dmrs_plan_destroy(plan);
+  if (!plan->d_jobs.upload(jobs)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload DM-RS jobs");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -591,7 +547,8 @@ int srsgpu_pdsch_dmrs_plan_execute(const srsgpu_pdsch_dmrs_plan* plan, uint32_t*
   if (plan == nullptr || d_grids == nullptr) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
-  launch_pdsch_dmrs(plan->d_jobs, plan->nof_jobs, plan->max_pilots, d_grids, plan->d_seq, static_cast<hipStream_t>(stream));
+  launch_pdsch_dmrs(plan->d_jobs.get(), plan->nof_jobs, plan->max_pilots, d_grids, plan->d_seq.get(),
+                    static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -600,12 +557,6 @@ void srsgpu_pdsch_dmrs_plan_destroy(srsgpu_pdsch_dmrs_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  if (plan->d_jobs != nullptr) {
-    (void)hipFree(plan->d_jobs);
-  }
-  if (plan->d_seq != nullptr) {
-    (void)hipFree(plan->d_seq);
   }
   delete plan;
 }

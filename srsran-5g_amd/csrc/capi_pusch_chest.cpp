@@ -14,12 +14,12 @@ static_assert(sizeof(srsgpu_pusch_chest_config) == 32, "srsgpu_pusch_chest_confi
 
 struct srsgpu_pusch_chest_plan {
   srsgpu_context* ctx        = nullptr;
-  chest_job*      d_jobs     = nullptr;
+  device_buffer<chest_job> d_jobs;
   int             nof_jobs   = 0;
   chest_geom      geom       = {};  ///< Plan-wide maxima (LDS sizing).
-  uint32_t*       d_seq      = nullptr;  ///< DM-RS sequence words of every job (plan lifetime).
-  uint16_t*       d_crbs     = nullptr;  ///< CRB lists of the CRB-mask transmissions (relative to their first CRB).
-  float2*         d_lp       = nullptr;  ///< Low-PAPR DM-RS sequences of the transform-precoded transmissions.
+  device_buffer<uint32_t> d_seq;  ///< DM-RS sequence words of every job (plan lifetime).
+  device_buffer<uint16_t> d_crbs;  ///< CRB lists of the CRB-mask transmissions (relative to their first CRB).
+  device_buffer<float2>   d_lp;  ///< Low-PAPR DM-RS sequences of the transform-precoded transmissions.
 };
 
 namespace {
@@ -363,7 +363,7 @@ int srsgpu_pusch_chest_plan_create_ex(srsgpu_context*                  ctx,
   if (r != SRSGPU_OK) {
     return r;
   }
-  auto* plan     = new srsgpu_pusch_chest_plan();
+  plan_ptr<srsgpu_pusch_chest_plan> plan(new srsgpu_pusch_chest_plan());
   plan->ctx      = ctx;
   plan->nof_jobs = static_cast<int>(jobs.size());
   chest_geom& g = plan->geom;
@@ -377,7 +377,6 @@ int srsgpu_pusch_chest_plan_create_ex(srsgpu_context*                  ctx,
     g.max_dft    = std::max<int>(g.max_dft, jb.ta_dft);
   }
   if (pusch_chest_lds_bytes(g) > 160 * 1024) {
-    delete plan;
     return fail(SRSGPU_ERR_INVALID_ARG, "channel estimation job too large for the LDS");
   }
   // DM-RS sequences, resident: per job and DM-RS symbol the words the kernel stages (from the allocation's first
@@ -396,31 +395,19 @@ int srsgpu_pusch_chest_plan_create_ex(srsgpu_context*                  ctx,
     }
     base += jb.nof_dmrs * nw;
   }
-  if (build_gold_sequences(ctx, c_inits, nwords, offsets, &plan->d_seq, &wstart) != SRSGPU_OK) {
-    srsgpu_pusch_chest_plan_destroy(plan);
+  if (build_gold_sequences(ctx, c_inits, nwords, offsets, plan->d_seq, &wstart) != SRSGPU_OK) {
     return SRSGPU_ERR_HIP;
   }
-  if (!lp_table.empty() &&
-      (hipMalloc(&plan->d_lp, lp_table.size() * sizeof(float2)) != hipSuccess ||
-       hipMemcpy(plan->d_lp, lp_table.data(), lp_table.size() * sizeof(float2), hipMemcpyHostToDevice) !=
-           hipSuccess)) {
-    srsgpu_pusch_chest_plan_destroy(plan);
+  if (!plan->d_lp.upload(lp_table)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload low-PAPR sequences");
   }
-  if (!crb_lists.empty() &&
-      (hipMalloc(&plan->d_crbs, crb_lists.size() * sizeof(uint16_t)) != hipSuccess ||
-       hipMemcpy(plan->d_crbs, crb_lists.data(), crb_lists.size() * sizeof(uint16_t), hipMemcpyHostToDevice) !=
-           hipSuccess)) {
-    srsgpu_pusch_chest_plan_destroy(plan);
+  if (!plan->d_crbs.upload(crb_lists)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload CRB lists");
   }
-  if (!jobs.empty() && (hipMalloc(&plan->d_jobs, jobs.size() * sizeof(chest_job)) != hipSuccess ||
-                        hipMemcpy(plan->d_jobs, jobs.data(), jobs.size() * sizeof(chest_job), hipMemcpyHostToDevice) !=
-                            hipSuccess)) {
-    srsgpu_pusch_chest_plan_destroy(plan);
+  if (!plan->d_jobs.upload(jobs)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload channel estimation jobs");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -434,8 +421,8 @@ int srsgpu_pusch_chest_plan_execute(const srsgpu_pusch_chest_plan* plan,
   if (plan == nullptr || d_grids == nullptr || d_ch_estimates == nullptr || d_noise_var == nullptr) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
-  launch_pusch_chest(plan->d_lp, plan->d_crbs, plan->d_jobs, plan->nof_jobs, plan->geom, d_grids, d_ch_estimates, d_noise_var, d_metrics,
-                     plan->d_seq, static_cast<hipStream_t>(stream));
+  launch_pusch_chest(plan->d_lp.get(), plan->d_crbs.get(), plan->d_jobs.get(), plan->nof_jobs, plan->geom, d_grids,
+                     d_ch_estimates, d_noise_var, d_metrics, plan->d_seq.get(), static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -458,8 +445,8 @@ int srsgpu_pusch_chest_plan_execute_copy(const srsgpu_pusch_chest_plan* plan,
   if (plan->nof_jobs <= 0) {
     return srsgpu_copy_spans(d_spans, nof_spans, max_bytes, stream);
   }
-  launch_pusch_chest(plan->d_lp, plan->d_crbs, plan->d_jobs, plan->nof_jobs, plan->geom, d_grids, d_ch_estimates,
-                     d_noise_var, d_metrics, plan->d_seq, static_cast<hipStream_t>(stream), d_spans,
+  launch_pusch_chest(plan->d_lp.get(), plan->d_crbs.get(), plan->d_jobs.get(), plan->nof_jobs, plan->geom, d_grids,
+                     d_ch_estimates, d_noise_var, d_metrics, plan->d_seq.get(), static_cast<hipStream_t>(stream), d_spans,
                      static_cast<int>(nof_spans), max_bytes);
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
@@ -469,18 +456,6 @@ void srsgpu_pusch_chest_plan_destroy(srsgpu_pusch_chest_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  if (plan->d_jobs != nullptr) {
-    (void)hipFree(plan->d_jobs);
-  }
-  if (plan->d_seq != nullptr) {
-    (void)hipFree(plan->d_seq);
-  }
-  if (plan->d_crbs != nullptr) {
-    (void)hipFree(plan->d_crbs);
-  }
-  if (plan->d_lp != nullptr) {
-    (void)hipFree(plan->d_lp);
   }
   delete plan;
 }

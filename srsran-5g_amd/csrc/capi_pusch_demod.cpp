@@ -13,13 +13,13 @@ static_assert(SRSGPU_DEMOD_STATS == DEMOD_STATS_PER_TX, "statistics row layout")
 
 struct srsgpu_pusch_demodulator_plan {
   srsgpu_context*       ctx        = nullptr;
-  demod_desc*           d_desc     = nullptr;
-  mod_chunk*            d_chunks   = nullptr;
-  demod_tp_job*         d_tp_jobs  = nullptr;  ///< Transform-precoded (transmission, symbol) work items.
-  demap_pair_table*     d_tables   = nullptr;
-  uint32_t*             d_seq      = nullptr;  ///< Descrambling sequences of the transmissions (plan lifetime).
-  uint16_t*             d_crbs     = nullptr;  ///< Allocated CRB lists of the CRB-mask transmissions.
-  float*                d_acc      = nullptr;  ///< Statistics accumulators (zero between executes).
+  device_buffer<demod_desc>       d_desc;
+  device_buffer<mod_chunk>        d_chunks;
+  device_buffer<demod_tp_job>     d_tp_jobs;  ///< Transform-precoded (transmission, symbol) work items.
+  device_buffer<demap_pair_table> d_tables;
+  device_buffer<uint32_t>         d_seq;   ///< Descrambling sequences of the transmissions (plan lifetime).
+  device_buffer<uint16_t>         d_crbs;  ///< Allocated CRB lists of the CRB-mask transmissions.
+  device_buffer<float>            d_acc;   ///< Statistics accumulators (zero between executes).
   int                   nof_chunks = 0;
   int                   chunk_threads = 256;  ///< Lanes per chunk workgroup (launch_pusch_demodulate).
   int                   nof_tp_jobs = 0;
@@ -294,7 +294,7 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
   for (size_t t = 0; t < descs.size(); ++t) {
     descs[t].seq_word_offset = seq_off[t];
   }
-  auto* plan        = new srsgpu_pusch_demodulator_plan();
+  plan_ptr<srsgpu_pusch_demodulator_plan> plan(new srsgpu_pusch_demodulator_plan());
   plan->ctx         = ctx;
   plan->nof_chunks  = static_cast<int>(chunks.size());
   plan->nof_tp_jobs = static_cast<int>(tp_jobs.size());
@@ -302,17 +302,8 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
   plan->nof_llrs    = std::move(nllr);
   plan->seq_off     = seq_off;
   const bool work   = !chunks.empty() || !tp_jobs.empty();
-  if (work && build_gold_sequences(ctx, c_inits, nwords, seq_off, &plan->d_seq) != SRSGPU_OK) {
-    srsgpu_pusch_demodulator_plan_destroy(plan);
+  if (work && build_gold_sequences(ctx, c_inits, nwords, seq_off, plan->d_seq) != SRSGPU_OK) {
     return SRSGPU_ERR_HIP;
-  }
-  bool ok = hipMalloc(&plan->d_tables, tables.size() * sizeof(demap_pair_table)) == hipSuccess &&
-            hipMemcpy(plan->d_tables, tables.data(), tables.size() * sizeof(demap_pair_table),
-                      hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && work) {
-    ok = hipMalloc(&plan->d_desc, descs.size() * sizeof(demod_desc)) == hipSuccess &&
-         hipMemcpy(plan->d_desc, descs.data(), descs.size() * sizeof(demod_desc), hipMemcpyHostToDevice) ==
-             hipSuccess;
   }
   if (!chunks.empty()) {
     // Lanes per chunk from its REs: a few-PRB transmission's chunk is a few hundred REs, which 256 lanes finish in two
@@ -325,30 +316,12 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
     }
     plan->chunk_threads = small_plan ? 256 : (most <= 384 ? 64 : (most <= 768 ? 128 : 256));
   }
-  if (ok && !chunks.empty()) {
-    ok = hipMalloc(&plan->d_chunks, chunks.size() * sizeof(mod_chunk)) == hipSuccess &&
-         hipMemcpy(plan->d_chunks, chunks.data(), chunks.size() * sizeof(mod_chunk), hipMemcpyHostToDevice) ==
-             hipSuccess;
-  }
-  if (ok && !tp_jobs.empty()) {
-    ok = hipMalloc(&plan->d_tp_jobs, tp_jobs.size() * sizeof(demod_tp_job)) == hipSuccess &&
-         hipMemcpy(plan->d_tp_jobs, tp_jobs.data(), tp_jobs.size() * sizeof(demod_tp_job), hipMemcpyHostToDevice) ==
-             hipSuccess;
-  }
-  if (ok && !crb_lists.empty()) {
-    ok = hipMalloc(&plan->d_crbs, crb_lists.size() * sizeof(uint16_t)) == hipSuccess &&
-         hipMemcpy(plan->d_crbs, crb_lists.data(), crb_lists.size() * sizeof(uint16_t), hipMemcpyHostToDevice) ==
-             hipSuccess;
-  }
-  if (ok && nof_tx > 0) {
-    const size_t acc_bytes = static_cast<size_t>(nof_tx) * DEMOD_ACC_PER_TX * sizeof(float);
-    ok = hipMalloc(&plan->d_acc, acc_bytes) == hipSuccess && hipMemset(plan->d_acc, 0, acc_bytes) == hipSuccess;
-  }
-  if (!ok) {
-    srsgpu_pusch_demodulator_plan_destroy(plan);
+  if (!plan->d_tables.upload(tables) || (work && !plan->d_desc.upload(descs)) || !plan->d_chunks.upload(chunks) ||
+      !plan->d_tp_jobs.upload(tp_jobs) || !plan->d_crbs.upload(crb_lists) ||
+      !plan->d_acc.alloc_zeroed(static_cast<size_t>(nof_tx) * DEMOD_ACC_PER_TX)) {
     return fail(SRSGPU_ERR_HIP, "failed to upload demodulator descriptors");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -384,13 +357,14 @@ int srsgpu_pusch_demodulator_plan_execute_ex(const srsgpu_pusch_demodulator_plan
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
   const hipStream_t s   = static_cast<hipStream_t>(stream);
-  float*            acc = d_stats != nullptr ? plan->d_acc : nullptr;
-  launch_pusch_demodulate(plan->d_desc, plan->d_chunks, plan->nof_chunks, plan->chunk_threads, plan->d_tables,
-                          d_grids, d_ch_estimates, d_noise_var, d_llrs, plan->d_seq, plan->d_crbs, acc, s);
-  launch_pusch_demodulate_tp(plan->d_desc, plan->d_tp_jobs, plan->nof_tp_jobs, plan->d_tables, d_grids,
-                             d_ch_estimates, d_noise_var, d_llrs, plan->d_seq, plan->d_crbs, acc, s);
+  float*            acc = d_stats != nullptr ? plan->d_acc.get() : nullptr;
+  launch_pusch_demodulate(plan->d_desc.get(), plan->d_chunks.get(), plan->nof_chunks, plan->chunk_threads,
+                          plan->d_tables.get(), d_grids, d_ch_estimates, d_noise_var, d_llrs, plan->d_seq.get(),
+                          plan->d_crbs.get(), acc, s);
+  launch_pusch_demodulate_tp(plan->d_desc.get(), plan->d_tp_jobs.get(), plan->nof_tp_jobs, plan->d_tables.get(), d_grids,
+                             d_ch_estimates, d_noise_var, d_llrs, plan->d_seq.get(), plan->d_crbs.get(), acc, s);
   if (d_stats != nullptr) {
-    launch_pusch_demod_stats(plan->d_acc, d_stats, plan->nof_tx, s);
+    launch_pusch_demod_stats(plan->d_acc.get(), d_stats, plan->nof_tx, s);
   }
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
@@ -400,13 +374,6 @@ void srsgpu_pusch_demodulator_plan_destroy(srsgpu_pusch_demodulator_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  for (void* p : {static_cast<void*>(plan->d_desc), static_cast<void*>(plan->d_chunks),
-                  static_cast<void*>(plan->d_tp_jobs), static_cast<void*>(plan->d_tables),
-                  static_cast<void*>(plan->d_seq), static_cast<void*>(plan->d_crbs), static_cast<void*>(plan->d_acc)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
   }
   delete plan;
 }
@@ -425,7 +392,7 @@ extern "C" int srsgpu_pusch_demodulator_plan_scrambling(const srsgpu_pusch_demod
   if (nwords == 0) {
     return SRSGPU_OK;
   }
-  HIP_TRY(hipMemcpyAsync(d_words, plan->d_seq + plan->seq_off[tx], nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+  HIP_TRY(hipMemcpyAsync(d_words, plan->d_seq.get() + plan->seq_off[tx], nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                          static_cast<hipStream_t>(stream)));
   return SRSGPU_OK;
 }

@@ -12,7 +12,7 @@ static_assert(sizeof(srsgpu_uci_field_config) == 12, "srsgpu_uci_field_config la
 
 struct srsgpu_uci_decoder_plan {
   srsgpu_context* ctx        = nullptr;
-  uci_field_desc* d_desc     = nullptr;
+  device_buffer<uci_field_desc> d_desc;
   uint32_t        nof_fields = 0;
   bool            uses[3]    = {false, false, false};  ///< Sources some field reads.
 };
@@ -71,20 +71,14 @@ int srsgpu_uci_decoder_plan_create(srsgpu_context*                ctx,
   }
   std::lock_guard<std::mutex> lock(ctx->mtx);
   HIP_TRY(hipSetDevice(ctx->device));
-  auto* plan       = new srsgpu_uci_decoder_plan();
+  plan_ptr<srsgpu_uci_decoder_plan> plan(new srsgpu_uci_decoder_plan());
   plan->ctx        = ctx;
   plan->nof_fields = nof_fields;
   std::copy(uses, uses + 3, plan->uses);
-  if (nof_fields > 0) {
-    const bool ok = hipMalloc(&plan->d_desc, descs.size() * sizeof(uci_field_desc)) == hipSuccess &&
-                    hipMemcpy(plan->d_desc, descs.data(), descs.size() * sizeof(uci_field_desc),
-                              hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-      srsgpu_uci_decoder_plan_destroy(plan);
-      return fail(SRSGPU_ERR_HIP, "failed to upload the UCI field descriptors");
-    }
+  if (!plan->d_desc.upload(descs)) {
+    return fail(SRSGPU_ERR_HIP, "failed to upload the UCI field descriptors");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -103,7 +97,7 @@ int srsgpu_uci_decoder_plan_execute(const srsgpu_uci_decoder_plan* plan,
       (plan->uses[2] && d_src2 == nullptr)) {
     return fail(SRSGPU_ERR_INVALID_ARG, "an input stream the plan reads is NULL");
   }
-  launch_uci_decode(plan->d_desc, plan->nof_fields, d_src0, d_src1, d_src2, d_msgs, d_status,
+  launch_uci_decode(plan->d_desc.get(), plan->nof_fields, d_src0, d_src1, d_src2, d_msgs, d_status,
                     static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
@@ -113,9 +107,6 @@ void srsgpu_uci_decoder_plan_destroy(srsgpu_uci_decoder_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  if (plan->d_desc != nullptr) {
-    (void)hipFree(plan->d_desc);
   }
   delete plan;
 }

@@ -15,10 +15,10 @@ static_assert(sizeof(srsgpu_uci_polar_field_config) == 16, "srsgpu_uci_polar_fie
 
 struct srsgpu_uci_polar_decoder_plan {
   srsgpu_context*       ctx        = nullptr;
-  uci_polar_field_desc* d_fields   = nullptr;
-  uci_polar_code_desc*  d_codes    = nullptr;
-  uint32_t*             d_ops      = nullptr;
-  uint16_t*             d_tables   = nullptr;
+  device_buffer<uci_polar_field_desc> d_fields;
+  device_buffer<uci_polar_code_desc>  d_codes;
+  device_buffer<uint32_t>             d_ops;
+  device_buffer<uint16_t>             d_tables;
   uint32_t              nof_fields = 0;
   bool                  uses[3]    = {false, false, false};  ///< Sources some field reads.
 };
@@ -26,14 +26,6 @@ struct srsgpu_uci_polar_decoder_plan {
 namespace {
 
 constexpr uint32_t MIN_BITS = 12, MAX_BITS = 1706;  // uci_decoder_impl.cpp:30 and uci_decoder_impl.h:74
-
-template <typename T>
-bool upload(T** d_ptr, const std::vector<T>& host)
-{
-  const size_t bytes = std::max<size_t>(host.size(), 1) * sizeof(T);
-  return hipMalloc(d_ptr, bytes) == hipSuccess &&
-         (host.empty() || hipMemcpy(*d_ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
-}
 
 } // namespace
 
@@ -113,19 +105,16 @@ int srsgpu_uci_polar_decoder_plan_create(srsgpu_context*                      ct
   }
   std::lock_guard<std::mutex> lock(ctx->mtx);
   HIP_TRY(hipSetDevice(ctx->device));
-  auto* plan       = new srsgpu_uci_polar_decoder_plan();
+  plan_ptr<srsgpu_uci_polar_decoder_plan> plan(new srsgpu_uci_polar_decoder_plan());
   plan->ctx        = ctx;
   plan->nof_fields = nof_fields;
   std::copy(uses, uses + 3, plan->uses);
-  if (nof_fields > 0) {
-    const bool ok = upload(&plan->d_fields, fields) && upload(&plan->d_codes, codes) && upload(&plan->d_ops, ops) &&
-                    upload(&plan->d_tables, tables);
-    if (!ok) {
-      srsgpu_uci_polar_decoder_plan_destroy(plan);
-      return fail(SRSGPU_ERR_HIP, "failed to upload the UCI polar decoder tables");
-    }
+  // With a field there is a code, and every code has operations and tables: none of the four is empty then.
+  if (!plan->d_fields.upload(fields) || !plan->d_codes.upload(codes) || !plan->d_ops.upload(ops) ||
+      !plan->d_tables.upload(tables)) {
+    return fail(SRSGPU_ERR_HIP, "failed to upload the UCI polar decoder tables");
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -144,8 +133,8 @@ int srsgpu_uci_polar_decoder_plan_execute(const srsgpu_uci_polar_decoder_plan* p
       (plan->uses[2] && d_src2 == nullptr)) {
     return fail(SRSGPU_ERR_INVALID_ARG, "an input stream the plan reads is NULL");
   }
-  launch_uci_polar_decode(plan->d_fields, plan->nof_fields, plan->d_codes, plan->d_ops, plan->d_tables, d_src0, d_src1,
-                          d_src2, d_msgs, d_status, static_cast<hipStream_t>(stream));
+  launch_uci_polar_decode(plan->d_fields.get(), plan->nof_fields, plan->d_codes.get(), plan->d_ops.get(),
+                          plan->d_tables.get(), d_src0, d_src1, d_src2, d_msgs, d_status, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -154,12 +143,6 @@ void srsgpu_uci_polar_decoder_plan_destroy(srsgpu_uci_polar_decoder_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  for (void* p : {static_cast<void*>(plan->d_fields), static_cast<void*>(plan->d_codes), static_cast<void*>(plan->d_ops),
-                  static_cast<void*>(plan->d_tables)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
   }
   delete plan;
 }

@@ -12,10 +12,10 @@ static_assert(sizeof(srsgpu_ulsch_demux_config) == 64, "srsgpu_ulsch_demux_confi
 
 struct srsgpu_ulsch_demux_plan {
   srsgpu_context*                    ctx        = nullptr;
-  ulsch_demux_desc*                  d_desc     = nullptr;
-  ulsch_demux_route*                 d_routes   = nullptr;
-  mod_chunk*                         d_chunks   = nullptr;
-  uint32_t*                          d_seq      = nullptr;
+  device_buffer<ulsch_demux_desc>    d_desc;
+  device_buffer<ulsch_demux_route>   d_routes;
+  device_buffer<mod_chunk>           d_chunks;
+  device_buffer<uint32_t>            d_seq;
   int                                nof_chunks = 0;
   std::vector<std::array<uint32_t, 5>> nof_llrs;  ///< Per transmission: codeword, UL-SCH, HARQ-ACK, CSI-1, CSI-2.
   std::vector<std::array<std::array<uint32_t, 14>, 5>> symbol_llrs;  ///< The same per OFDM symbol.
@@ -222,32 +222,20 @@ int srsgpu_ulsch_demux_plan_create(srsgpu_context*                  ctx,
   for (uint32_t t = 0; t < nof_tx; ++t) {
     descs[t].seq_word_offset = seq_off[t];
   }
-  auto* plan       = new srsgpu_ulsch_demux_plan();
+  plan_ptr<srsgpu_ulsch_demux_plan> plan(new srsgpu_ulsch_demux_plan());
   plan->ctx        = ctx;
   plan->nof_chunks = static_cast<int>(chunks.size());
   plan->nof_llrs   = std::move(counts);
   plan->symbol_llrs = std::move(sym_counts);
   if (!chunks.empty()) {
-    if (build_gold_sequences(ctx, c_inits, nwords, seq_off, &plan->d_seq) != SRSGPU_OK) {
-      srsgpu_ulsch_demux_plan_destroy(plan);
+    if (build_gold_sequences(ctx, c_inits, nwords, seq_off, plan->d_seq) != SRSGPU_OK) {
       return SRSGPU_ERR_HIP;
     }
-    const bool ok =
-        hipMalloc(&plan->d_desc, descs.size() * sizeof(ulsch_demux_desc)) == hipSuccess &&
-        hipMemcpy(plan->d_desc, descs.data(), descs.size() * sizeof(ulsch_demux_desc), hipMemcpyHostToDevice) ==
-            hipSuccess &&
-        hipMalloc(&plan->d_routes, routes.size() * sizeof(ulsch_demux_route)) == hipSuccess &&
-        hipMemcpy(plan->d_routes, routes.data(), routes.size() * sizeof(ulsch_demux_route), hipMemcpyHostToDevice) ==
-            hipSuccess &&
-        hipMalloc(&plan->d_chunks, chunks.size() * sizeof(mod_chunk)) == hipSuccess &&
-        hipMemcpy(plan->d_chunks, chunks.data(), chunks.size() * sizeof(mod_chunk), hipMemcpyHostToDevice) ==
-            hipSuccess;
-    if (!ok) {
-      srsgpu_ulsch_demux_plan_destroy(plan);
+    if (!plan->d_desc.upload(descs) || !plan->d_routes.upload(routes) || !plan->d_chunks.upload(chunks)) {
       return fail(SRSGPU_ERR_HIP, "failed to upload the demultiplexer routing");
     }
   }
-  *plan_out = plan;
+  *plan_out = plan.release();
   return SRSGPU_OK;
 }
 
@@ -283,8 +271,8 @@ int srsgpu_ulsch_demux_plan_execute(const srsgpu_ulsch_demux_plan* plan,
       return fail(SRSGPU_ERR_INVALID_ARG, "an output stream the plan writes is NULL");
     }
   }
-  launch_ulsch_demux(plan->d_desc, plan->d_routes, plan->d_chunks, plan->nof_chunks, d_llrs, d_sch, d_harq, d_csi1,
-                     d_csi2, plan->d_seq, static_cast<hipStream_t>(stream));
+  launch_ulsch_demux(plan->d_desc.get(), plan->d_routes.get(), plan->d_chunks.get(), plan->nof_chunks, d_llrs, d_sch,
+                     d_harq, d_csi1, d_csi2, plan->d_seq.get(), static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return SRSGPU_OK;
 }
@@ -293,12 +281,6 @@ void srsgpu_ulsch_demux_plan_destroy(srsgpu_ulsch_demux_plan* plan)
 {
   if (plan == nullptr) {
     return;
-  }
-  for (void* p : {static_cast<void*>(plan->d_desc), static_cast<void*>(plan->d_routes),
-                  static_cast<void*>(plan->d_chunks), static_cast<void*>(plan->d_seq)}) {
-    if (p != nullptr) {
-      (void)hipFree(p);
-    }
   }
   delete plan;
 }

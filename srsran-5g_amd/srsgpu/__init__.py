@@ -496,6 +496,8 @@ def load_library(path: str = LIB_PATH):
     for name in ("srsgpu_pusch_decoder_plan", "srsgpu_pdsch_encoder_plan"):
         getattr(lib, name + "_enable_timing").argtypes = [P, ctypes.c_int]
         getattr(lib, name + "_stage_times").argtypes = [P, P, ctypes.POINTER(ctypes.c_uint32)]
+    lib.srsgpu_debug_live_device_buffers.argtypes = []
+    lib.srsgpu_debug_live_device_buffers.restype = ctypes.c_int64
     _lib = lib
     return lib
 
@@ -534,7 +536,13 @@ EXPORTED_SYMBOLS = [
     "srsgpu_pusch_chest_plan_execute_copy",
     "srsgpu_pdsch_dmrs_plan_create", "srsgpu_pdsch_dmrs_plan_create_ex", "srsgpu_pdsch_dmrs_plan_execute", "srsgpu_pdsch_dmrs_plan_destroy",
     "srsgpu_pdcch_plan_create", "srsgpu_pdcch_plan_execute", "srsgpu_pdcch_plan_destroy",
+    "srsgpu_debug_live_device_buffers",
 ]
+
+
+def live_device_buffers() -> int:
+    """srsgpu_debug_live_device_buffers: device allocations the library's contexts and plans hold right now."""
+    return int(load_library().srsgpu_debug_live_device_buffers())
 
 
 def _stage_times(prefix, handle, n):
@@ -606,8 +614,26 @@ OPTION_DEFAULTS = {OPTION_DECODER_SPLIT: -1, OPTION_DECODER_PAIRS: 0, OPTION_DEC
                    OPTION_ENCODER_BYTE_KERNEL: 0, OPTION_ENCODER_ZERO_OUTPUT: 0, OPTION_DECODER_TB_FOLD: 1}
 
 
-class Context:
+class _Handle:
+    """Owner of one C-ABI object: `handle`, given back once to the library function named by `_destroy`."""
+    handle = None
+    _destroy = None
+
+    def close(self):
+        if self.handle:
+            getattr(_lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class Context(_Handle):
     """srsgpu_context: one per GPU (one process per GPU)."""
+    _destroy = "srsgpu_context_destroy"
 
     def __init__(self, device: int = 0):
         lib = load_library()
@@ -645,17 +671,6 @@ class Context:
                     self.set_option(k, v)
         return scope()
 
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_context_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
 
 @dataclass
 class CodeblockDecodeConfig:
@@ -692,8 +707,9 @@ def make_configs(cfgs: Sequence[CodeblockDecodeConfig], nof_llrs: Sequence[int],
     return arr
 
 
-class LdpcDecoderPlan:
+class LdpcDecoderPlan(_Handle):
     """srsgpu_ldpc_decoder_plan: validated, device-resident batch of decoder work (hipGraph-capturable execute)."""
+    _destroy = "srsgpu_ldpc_decoder_plan_destroy"
 
     def __init__(self, ctx: Context, impl: int, cfg_array):
         self.ctx = ctx
@@ -706,17 +722,6 @@ class LdpcDecoderPlan:
     def execute(self, d_llrs, d_out, d_iters, stream=None):
         _check(_lib.srsgpu_ldpc_decoder_plan_execute(self.handle, _dptr(d_llrs), _dptr(d_out), _dptr(d_iters),
                                                      _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_ldpc_decoder_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 def unpack_bits(packed: np.ndarray, nbits: int) -> np.ndarray:
@@ -771,8 +776,9 @@ class LdpcDecoder:
         return results
 
 
-class PuschCbPlan:
+class PuschCbPlan(_Handle):
     """srsgpu_pusch_cb_plan: rate dematching + HARQ combining + LDPC decoding + CB CRC for a batch of codeblocks."""
+    _destroy = "srsgpu_pusch_cb_plan_destroy"
 
     def __init__(self, ctx: Context, impl: int, cfg_array):
         self.ctx = ctx
@@ -785,17 +791,6 @@ class PuschCbPlan:
     def execute(self, d_llrs, d_harq, d_out, d_iters, d_cb_crc_ok=None, stream=None):
         _check(_lib.srsgpu_pusch_cb_plan_execute(self.handle, _dptr(d_llrs), _dptr(d_harq), _dptr(d_out),
                                                  _dptr(d_iters), _dptr(d_cb_crc_ok), _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pusch_cb_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 @dataclass
@@ -898,8 +893,9 @@ def make_pdsch_configs(tbs_bytes: Sequence[int], tbs: Sequence[PdschTransportBlo
     return arr, to, co, cw_offsets
 
 
-class PdschEncoderPlan:
+class PdschEncoderPlan(_Handle):
     """srsgpu_pdsch_encoder_plan: TB CRC + segmentation + CB CRC + LDPC + rate matching of a slot's TBs."""
+    _destroy = "srsgpu_pdsch_encoder_plan_destroy"
 
     def __init__(self, ctx: Context, cfg_array):
         self.ctx = ctx
@@ -920,17 +916,6 @@ class PdschEncoderPlan:
     def stage_times(self):
         """([ms TB CRC, ms encode], number of executes) accumulated since the previous call."""
         return _stage_times("srsgpu_pdsch_encoder_plan", self.handle, 2)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pdsch_encoder_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PdschEncoder:
@@ -1063,9 +1048,10 @@ def make_pdsch_mod_configs(mods: Sequence[PdschModulation], cw_offsets: Sequence
     return arr
 
 
-class PdschModulatorPlan:
+class PdschModulatorPlan(_Handle):
     """srsgpu_pdsch_modulator_plan: scrambling, modulation, layer mapping, precoding and RE mapping of a batch of
     PDSCH transmissions into bf16 resource grids (grid_nof_ports x 14 x 12 * grid_nof_prb, uint32 re | im << 16)."""
+    _destroy = "srsgpu_pdsch_modulator_plan_destroy"
 
     def __init__(self, ctx: Context, cfg_array, grid_nof_prb: int, grid_nof_ports: int = 4, exts=None):
         self.ctx = ctx
@@ -1087,17 +1073,6 @@ class PdschModulatorPlan:
     def execute(self, d_codewords, d_grids, stream=None):
         _check(_lib.srsgpu_pdsch_modulator_plan_execute(self.handle, _dptr(d_codewords), _dptr(d_grids),
                                                         _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pdsch_modulator_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PdschModulator:
@@ -1196,8 +1171,9 @@ def make_pdsch_dmrs_configs(dmrs: Sequence[PdschDmrs], grid_index: Sequence[int]
     return arr
 
 
-class PdschDmrsPlan:
+class PdschDmrsPlan(_Handle):
     """srsgpu_pdsch_dmrs_plan: PDSCH DM-RS generation, cover codes, precoding and mapping into bf16 grids."""
+    _destroy = "srsgpu_pdsch_dmrs_plan_destroy"
 
     def __init__(self, ctx: Context, cfg_array, grid_nof_prb: int, grid_nof_ports: int = 4, exts=None):
         self.ctx = ctx
@@ -1213,17 +1189,6 @@ class PdschDmrsPlan:
 
     def execute(self, d_grids, stream=None):
         _check(_lib.srsgpu_pdsch_dmrs_plan_execute(self.handle, _dptr(d_grids), _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pdsch_dmrs_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 @dataclass
@@ -1283,10 +1248,11 @@ def make_pdcch_configs(dcis: Sequence[Pdcch], payload_offsets: Sequence[int]):
     return arr
 
 
-class PdcchPlan:
+class PdcchPlan(_Handle):
     """srsgpu_pdcch_plan: every DCI of a batch of slots encoded, modulated and mapped with its DM-RS in one launch.
     dcis: Pdcch entries; payload_offsets: byte offset of each DCI's packed payload in the buffer given to execute()
     (default: pdcch_pack_payloads order). self.payload_bytes: the least size of that buffer."""
+    _destroy = "srsgpu_pdcch_plan_destroy"
 
     def __init__(self, ctx: Context, dcis: Sequence[Pdcch], grid_nof_prb: int, grid_nof_ports: int = 4,
                  nof_grids: Optional[int] = None, payload_offsets: Optional[Sequence[int]] = None):
@@ -1311,17 +1277,6 @@ class PdcchPlan:
         _check(_lib.srsgpu_pdcch_plan_execute(self.handle, _dptr(d_payloads), int(d_payloads.numel() * d_payloads.element_size()),
                                               _dptr(d_grids),
                                               _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pdcch_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PdcchProcessor:
@@ -1396,10 +1351,11 @@ def make_pusch_demod_configs(demods: Sequence[PuschDemodulation], grid_index: Se
     return arr, offs, off
 
 
-class PuschDemodulatorPlan:
+class PuschDemodulatorPlan(_Handle):
     """srsgpu_pusch_demodulator_plan: equalization + soft demapping + descrambling of a batch of PUSCH transmissions
     from rx grids (nslots, ports, 14, nsc) and channel estimates (nslots, 4 layers, ports, 14, nsc) (uint32 bf16 pairs)
     and noise variances (ntx, 4) float32 into int8 codeword LLRs."""
+    _destroy = "srsgpu_pusch_demodulator_plan_destroy"
 
     def __init__(self, ctx: Context, cfg_array, grid_nof_prb: int, grid_nof_ports: int = 4, exts=None):
         self.ctx = ctx
@@ -1428,17 +1384,6 @@ class PuschDemodulatorPlan:
             _check(_lib.srsgpu_pusch_demodulator_plan_execute_ex(self.handle, _dptr(d_grids), _dptr(d_ch_est),
                                                                  _dptr(d_noise_var), _dptr(d_llrs), _dptr(d_stats),
                                                                  _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pusch_demodulator_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PuschDemodulator:
@@ -1516,10 +1461,11 @@ def make_pusch_chest_configs(ests: Sequence[PuschChannelEstimation], grid_index:
     return arr
 
 
-class PuschChannelEstimatorPlan:
+class PuschChannelEstimatorPlan(_Handle):
     """srsgpu_pusch_chest_plan: DM-RS channel estimation of a batch of PUSCH transmissions from rx grids
     (S, Pg, 14, nsc) into estimates (S, 4, Pg, 14, nsc) (uint32 bf16 pairs), noise variances (ntx, 4) and optional
     metrics (ntx, 4, CHEST_METRICS: RSRP, EPRE, noise variance, SNR, TA seconds, CFO Hz or NaN, 0, 0)."""
+    _destroy = "srsgpu_pusch_chest_plan_destroy"
 
     def __init__(self, ctx: Context, cfg_array, grid_nof_prb: int, grid_nof_ports: int = 4, exts=None):
         self.ctx = ctx
@@ -1545,17 +1491,6 @@ class PuschChannelEstimatorPlan:
                                                          _dptr(d_noise_var), _dptr(d_metrics), _dptr(d), len(spans),
                                                          int(nbytes.max()), _stream_handle(stream)))
         return d
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pusch_chest_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PuschChannelEstimator:
@@ -1608,9 +1543,10 @@ class UlschDemultiplexing:
     csi2_first_symbol: int = 0  # CSI Part 2 from this symbol on (the processor's set_csi_part2 point; 0: from the start)
 
 
-class UlschDemuxPlan:
+class UlschDemuxPlan(_Handle):
     """srsgpu_ulsch_demux_plan: UCI-on-PUSCH demultiplexing of a batch of codewords (int8 LLRs) into the UL-SCH,
     HARQ-ACK, CSI Part 1 and CSI Part 2 streams."""
+    _destroy = "srsgpu_ulsch_demux_plan_destroy"
 
     STREAMS = ("codeword", "sch", "harq", "csi1", "csi2")
 
@@ -1657,17 +1593,6 @@ class UlschDemuxPlan:
         _check(_lib.srsgpu_ulsch_demux_plan_execute(self.handle, _dptr(d_llrs), _dptr(d_sch), _dptr(d_harq),
                                                     _dptr(d_csi1), _dptr(d_csi2), _stream_handle(stream)))
 
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_ulsch_demux_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
 
 class UlschDemultiplexer:
     """GPU counterpart of srsran::ulsch_demultiplex (ulsch_demultiplex_impl.cpp:199): demultiplex_batch() takes each
@@ -1696,9 +1621,10 @@ class UlschDemultiplexer:
         return res
 
 
-class UciDecoderPlan:
+class UciDecoderPlan(_Handle):
     """srsgpu_uci_decoder_plan: short-block UCI fields (1..11 bits) decoded in one launch. fields: UciFieldConfig
     entries, or (nof_bits, modulation_order, source, nof_enc_bits, llr_offset) tuples."""
+    _destroy = "srsgpu_uci_decoder_plan_destroy"
 
     def __init__(self, ctx: Context, fields):
         self.ctx = ctx
@@ -1720,17 +1646,6 @@ class UciDecoderPlan:
         (int16 / uint16, bit j = message bit j) and d_status (uint8, 1 valid) per field."""
         _check(_lib.srsgpu_uci_decoder_plan_execute(self.handle, _dptr(d_harq), _dptr(d_csi1), _dptr(d_csi2),
                                                     _dptr(d_msgs), _dptr(d_status), _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_uci_decoder_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class UciDecoder:
@@ -1777,11 +1692,12 @@ def uci_polar_unpack(words: np.ndarray, msg_word_offset: int, nof_bits: int) -> 
     return ((w[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(np.uint8).ravel()[:nof_bits]
 
 
-class UciPolarDecoderPlan:
+class UciPolarDecoderPlan(_Handle):
     """srsgpu_uci_polar_decoder_plan: polar-coded UCI fields (12..1706 bits) decoded in one launch, one wavefront per
     codeblock. fields: UciPolarFieldConfig entries, or (nof_bits, source, nof_enc_bits, llr_offset, msg_word_offset)
     tuples; a msg_word_offset of None packs the fields' words back to back in field order (self.msg_word_offsets,
     self.nof_msg_words)."""
+    _destroy = "srsgpu_uci_polar_decoder_plan_destroy"
 
     def __init__(self, ctx: Context, fields):
         self.ctx = ctx
@@ -1809,17 +1725,6 @@ class UciPolarDecoderPlan:
         (int32 / uint32 words, see srsgpu_uci_polar_decoder_plan_execute) and d_status (uint8, 1 valid) per field."""
         _check(_lib.srsgpu_uci_polar_decoder_plan_execute(self.handle, _dptr(d_harq), _dptr(d_csi1), _dptr(d_csi2),
                                                           _dptr(d_msgs), _dptr(d_status), _stream_handle(stream)))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_uci_polar_decoder_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class UciPolarDecoder:
@@ -1849,12 +1754,13 @@ class UciPolarDecoder:
         return bits, [bool(v) for v in status[: len(fields)]]
 
 
-class OfdmPlan:
+class OfdmPlan(_Handle):
     """srsgpu_ofdm_plan: OFDM slot modulation (inverse=True) or demodulation of nof_grids slots x nof_ports ports.
     Grids: (nof_grids, nof_ports, nsymb, 12 bw_rb) uint32 bf16 pairs; time buffer: nof_samples complex floats (as
     2 * nof_samples float32), slot of (grid, port) at sample_offset(grid, port).
     symbols=(first, count): a symbol-granularity plan of one slot (slot_indices holds one slot index) covering only
     those symbols (srsgpu_ofdm_*_symbols_plan_create; grid rows [port][symbol - first])."""
+    _destroy = "srsgpu_ofdm_plan_destroy"
 
     def __init__(self, ctx: Context, inverse: bool, numerology: int, bw_rb: int, dft_size: int, scale: float,
                  center_freq_hz: float, slot_indices: Sequence[int], nof_ports: int, cp_extended: bool = False,
@@ -1942,17 +1848,6 @@ class OfdmPlan:
         _check(_lib.srsgpu_ofdm_modulator_plan_execute_twin(self.handle, _dptr(d_grid), _dptr(d_twin), _dptr(d_samples),
                                                             _stream_handle(stream)))
 
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_ofdm_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
 
 class OfdmSlotModulator:
     """GPU counterpart of srsran::ofdm_slot_modulator (ofdm_modulator_impl.cpp:115): modulate(grid, slot) takes a
@@ -2033,8 +1928,9 @@ def make_pusch_tb_configs(tbs: Sequence[PuschTransportBlock], nof_cbs: Sequence[
     return arr, lo, ho, co, to
 
 
-class PuschDecoderPlan:
+class PuschDecoderPlan(_Handle):
     """srsgpu_pusch_decoder_plan (TB level)."""
+    _destroy = "srsgpu_pusch_decoder_plan_destroy"
 
     def __init__(self, ctx: Context, impl: int, cfg_array):
         self.ctx = ctx
@@ -2070,17 +1966,6 @@ class PuschDecoderPlan:
     def stage_times(self):
         """([ms dematch, ms decode, ms TB stage], number of executes) accumulated since the previous call."""
         return _stage_times("srsgpu_pusch_decoder_plan", self.handle, 3)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.srsgpu_pusch_decoder_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PuschDecoder:

@@ -23,6 +23,17 @@ def test_header_declares_api():
     assert "srsgpu_ldpc_decode" in fns and "srsgpu_context_create" in fns
 
 
+def test_device_memory_is_owned_by_device_buffer_only():
+    """The host layer allocates and frees device memory in one place, srsgpu::device_buffer (capi_internal.h): a plan
+    that calls hipMalloc / hipFree itself escapes the live-buffer count and the lifetime tests."""
+    csrc = os.path.join(ROOT, "srsran-5g_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".cpp", ".h")))
+    assert "capi_internal.h" in files and "capi.cpp" in files
+    users = [f for f in files
+             if any(call in open(os.path.join(csrc, f)).read() for call in ("hipMalloc(", "hipFree("))]
+    assert users == ["capi_internal.h"], users
+
+
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libsrsgpu_phy.so not built")
 def test_library_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout

@@ -205,8 +205,10 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
       return fail(SRSGPU_ERR_INVALID_ARG, "tx %u: codeword too long", t);
     }
     const uint64_t slot_elems = static_cast<uint64_t>(grid_nof_ports) * 14u * nsc;
-    if ((static_cast<uint64_t>(c.grid_index) + 1) * slot_elems * 4u >= (1ull << 32)) {
-      return fail(SRSGPU_ERR_INVALID_ARG, "tx %u: grid index beyond 32-bit element offsets", t);
+    // The kernels address the grids and the estimates (four layers per slot, four bytes per element) by unsigned
+    // 32-bit byte offsets (pusch_demodulator.hip load_re): the slot's estimates must end within 4 GiB.
+    if ((static_cast<uint64_t>(c.grid_index) + 1) * slot_elems * 4u * 4u > (1ull << 32)) {
+      return fail(SRSGPU_ERR_INVALID_ARG, "tx %u: grid index beyond 32-bit byte offsets", t);
     }
     const uint32_t first_sc = masked ? 0u : c.rb_start * 12u;  // CRB lists address absolute subcarriers
     d.grid_base       = static_cast<uint32_t>(c.grid_index * slot_elems) + first_sc;

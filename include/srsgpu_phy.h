@@ -441,6 +441,97 @@ int srsgpu_pdcch_plan_execute(const srsgpu_pdcch_plan* plan,
 void srsgpu_pdcch_plan_destroy(srsgpu_pdcch_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH Formats 0 and 1 — replaces srsran::pucch_processor::process(grid, format0_configuration) and
+ * process(grid, format1_batch_configuration) (lib/phy/upper/channel_processors/pucch/pucch_processor_impl.cpp:42 / :74)
+ * with the detectors behind them (pucch_detector_format0.cpp:114, pucch_detector_format1.cpp:156) for every Format 0
+ * PDU and every Format 1 resource (one PRB, or two with hopping, and all PUCCHs multiplexed on it) of a batch of
+ * slots, in one launch, from bf16 grids of the uplink plans' layout to the UCI bits and the channel state.
+ *
+ * PRBs are grid PRBs (the BWP start already added). Format 0 reads the listed grid ports; Format 1 reads grid ports
+ * 0..nof_rx_ports-1, as the reference's Format 1 detector does whatever its configuration lists. All powers are
+ * linear; the caller takes 10 log10. Group and sequence hopping are not supported (the reference terminates).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint16_t slot_index;           /* n_slot within the frame */
+  uint8_t  numerology;           /* 0..4 */
+  uint8_t  cp_extended;          /* 1: extended CP (numerology 2 only), 12 symbols per slot */
+  uint16_t starting_prb;
+  uint16_t second_hop_prb;       /* 0xffff: no hopping */
+  uint8_t  start_symbol_index;
+  uint8_t  nof_symbols;          /* 1 or 2 */
+  uint8_t  initial_cyclic_shift; /* 0..11 */
+  uint8_t  nof_harq_ack;         /* 0..2 */
+  uint16_t n_id;                 /* 0..1023 */
+  uint8_t  sr_opportunity;       /* 0 or 1 */
+  uint8_t  nof_ports;            /* 1..4 */
+  uint8_t  ports[4];             /* grid ports, in the order of format0_configuration::ports */
+  uint32_t grid_index;
+} srsgpu_pucch_f0_config;
+
+typedef struct {
+  uint16_t slot_index;
+  uint8_t  numerology;
+  uint8_t  cp_extended;
+  uint16_t starting_prb;
+  uint16_t second_hop_prb;       /* 0xffff: no hopping */
+  uint8_t  start_symbol_index;   /* 0..10 */
+  uint8_t  nof_symbols;          /* 4..14 */
+  uint16_t n_id;
+  uint8_t  nof_rx_ports;         /* grid ports 0..nof_rx_ports-1; times the hops one of 1, 2, 4, 8 */
+  uint8_t  reserved[3];
+  uint32_t grid_index;
+  uint32_t first_entry;          /* the resource's entries are f1_entries[first_entry .. first_entry + nof_entries) */
+  uint32_t nof_entries;          /* 1..84 */
+} srsgpu_pucch_f1_resource;
+
+typedef struct {
+  uint8_t initial_cyclic_shift;  /* 0..11 */
+  uint8_t time_domain_occ;       /* below the data symbols of the shorter hop */
+  uint8_t nof_harq_ack;          /* 0 (SR only), 1 or 2 */
+  uint8_t reserved;
+} srsgpu_pucch_f1_entry;
+
+/** One per Format 0 PDU, then one per Format 1 entry, in the caller's order. */
+typedef struct {
+  uint8_t  sr;                /* Format 0 with an SR opportunity: the SR bit; otherwise 0 */
+  uint8_t  harq_ack[2];       /* the detected HARQ-ACK bits (Format 1 SR only: harq_ack[0] is the detected bit) */
+  uint8_t  status;            /* 0 invalid, 1 valid */
+  float    detection_metric;  /* Format 0: best_metric; Format 1: the metric over its threshold */
+  float    epre;
+  float    rsrp;              /* Format 0: the chosen sequence's sum_corr, as the reference reports it */
+  float    noise_var;         /* Format 0: the chosen sequence's sum_noise_var; Format 1: the resource's variance */
+  uint32_t reserved[3];       /* written as zero */
+} srsgpu_pucch_result;
+
+typedef struct srsgpu_pucch_detector_plan srsgpu_pucch_detector_plan;
+
+/** Refuses what pucch_pdu_validator_impl::is_valid and the detectors' assertions refuse, and where the reference is
+ *  undefined: a Format 1 resource without entries, a time_domain_occ not below the data symbols of the shorter hop,
+ *  two entries of a resource with the same (cyclic shift, OCC), nof_rx_ports x hops outside {1, 2, 4, 8}, and a PRB,
+ *  port or grid outside the grids. */
+int srsgpu_pucch_detector_plan_create(srsgpu_context*                 ctx,
+                                      const srsgpu_pucch_f0_config*   f0,
+                                      uint32_t                        nof_f0,
+                                      const srsgpu_pucch_f1_resource* f1_resources,
+                                      uint32_t                        nof_f1,
+                                      const srsgpu_pucch_f1_entry*    f1_entries,
+                                      uint32_t                        nof_entries,
+                                      uint32_t                        grid_nof_prb,
+                                      uint32_t                        grid_nof_ports,
+                                      uint32_t                        nof_grids,
+                                      srsgpu_pucch_detector_plan**    plan);
+
+/** Detects every planned PDU and resource: reads d_grids (uint32 per RE: re | im << 16, bf16; nof_grids x ports x 14 x
+ *  12 PRBs) and writes the nof_f0 + nof_entries results. One launch, asynchronous on `stream`, allocation-free,
+ *  hipGraph-capturable. */
+int srsgpu_pucch_detector_plan_execute(const srsgpu_pucch_detector_plan* plan,
+                                       const uint32_t*                   d_grids,
+                                       srsgpu_pucch_result*              d_results,
+                                       void*                             stream);
+
+void srsgpu_pucch_detector_plan_destroy(srsgpu_pucch_detector_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

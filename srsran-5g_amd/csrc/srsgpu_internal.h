@@ -719,6 +719,17 @@ void launch_pdcch(const pdcch_desc*      d_descs,
                   const uint32_t*        d_x2_lane,
                   hipStream_t            stream);
 
+/// PUCCH Formats 0 and 1 (pucch_detector.hip): one wavefront per job (pucch_host.h), the entry words of the Format 1
+/// resources, the orthogonal sequences (pucch_w_table) and one 32-byte result per Format 0 PDU and Format 1 entry.
+struct pucch_job;
+void launch_pucch_detector(const pucch_job*     d_jobs,
+                           uint32_t             nof_jobs,
+                           const uint32_t*      d_entries,
+                           const float*         d_w,
+                           const uint32_t*      d_grids,
+                           srsgpu_pucch_result* d_results,
+                           hipStream_t          stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

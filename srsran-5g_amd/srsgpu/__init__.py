@@ -320,6 +320,64 @@ class PdcchConfig(ctypes.Structure):
 assert ctypes.sizeof(PdcchConfig) == 128
 
 
+class PucchF0Config(ctypes.Structure):
+    """srsgpu_pucch_f0_config (include/srsgpu_phy.h): pucch_detector::format0_configuration of one PDU (PRBs already
+    offset by the BWP start; second_hop_prb 0xffff = no hopping) and the grid it is read from."""
+    _fields_ = [
+        ("slot_index", ctypes.c_uint16),
+        ("numerology", ctypes.c_uint8),
+        ("cp_extended", ctypes.c_uint8),
+        ("starting_prb", ctypes.c_uint16),
+        ("second_hop_prb", ctypes.c_uint16),
+        ("start_symbol_index", ctypes.c_uint8),
+        ("nof_symbols", ctypes.c_uint8),
+        ("initial_cyclic_shift", ctypes.c_uint8),
+        ("nof_harq_ack", ctypes.c_uint8),
+        ("n_id", ctypes.c_uint16),
+        ("sr_opportunity", ctypes.c_uint8),
+        ("nof_ports", ctypes.c_uint8),
+        ("ports", ctypes.c_uint8 * 4),
+        ("grid_index", ctypes.c_uint32),
+    ]
+
+
+class PucchF1Resource(ctypes.Structure):
+    """srsgpu_pucch_f1_resource: the common configuration of the PUCCHs multiplexed on one PRB (two with hopping)."""
+    _fields_ = [
+        ("slot_index", ctypes.c_uint16),
+        ("numerology", ctypes.c_uint8),
+        ("cp_extended", ctypes.c_uint8),
+        ("starting_prb", ctypes.c_uint16),
+        ("second_hop_prb", ctypes.c_uint16),
+        ("start_symbol_index", ctypes.c_uint8),
+        ("nof_symbols", ctypes.c_uint8),
+        ("n_id", ctypes.c_uint16),
+        ("nof_rx_ports", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+        ("grid_index", ctypes.c_uint32),
+        ("first_entry", ctypes.c_uint32),
+        ("nof_entries", ctypes.c_uint32),
+    ]
+
+
+class PucchF1Entry(ctypes.Structure):
+    """srsgpu_pucch_f1_entry: one multiplexed PUCCH of a resource (an element of pucch_format1_map<unsigned>)."""
+    _fields_ = [
+        ("initial_cyclic_shift", ctypes.c_uint8),
+        ("time_domain_occ", ctypes.c_uint8),
+        ("nof_harq_ack", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+    ]
+
+
+assert ctypes.sizeof(PucchF0Config) == 24 and ctypes.sizeof(PucchF1Resource) == 28 and ctypes.sizeof(PucchF1Entry) == 4
+PUCCH_NO_HOP = 0xffff
+# srsgpu_pucch_result, 32 bytes: one per Format 0 PDU, then one per Format 1 entry.
+PUCCH_RESULT_DTYPE = np.dtype([("sr", "u1"), ("harq_ack", "u1", (2,)), ("status", "u1"), ("detection_metric", "<f4"),
+                               ("epre", "<f4"), ("rsrp", "<f4"), ("noise_var", "<f4"), ("reserved", "<u4", (3,))])
+assert PUCCH_RESULT_DTYPE.itemsize == 32
+
+
 class PuschChestConfig(ctypes.Structure):
     """srsgpu_pusch_chest_config (include/srsgpu_phy.h): dmrs_pusch_estimator::configuration of one transmission."""
     _fields_ = [
@@ -453,6 +511,12 @@ def load_library(path: str = LIB_PATH):
     lib.srsgpu_pdcch_plan_execute.argtypes = [P, P, ctypes.c_uint64, P, P]
     lib.srsgpu_pdcch_plan_destroy.argtypes = [P]
     lib.srsgpu_pdcch_plan_destroy.restype = None
+    lib.srsgpu_pucch_detector_plan_create.argtypes = [P, P, ctypes.c_uint32, P, ctypes.c_uint32, P, ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                      ctypes.POINTER(P)]
+    lib.srsgpu_pucch_detector_plan_execute.argtypes = [P, P, P, P]
+    lib.srsgpu_pucch_detector_plan_destroy.argtypes = [P]
+    lib.srsgpu_pucch_detector_plan_destroy.restype = None
     lib.srsgpu_pusch_chest_plan_create_ex.argtypes = [P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.POINTER(P)]
     lib.srsgpu_pdsch_dmrs_plan_destroy.argtypes = [P]
@@ -536,6 +600,7 @@ EXPORTED_SYMBOLS = [
     "srsgpu_pusch_chest_plan_execute_copy",
     "srsgpu_pdsch_dmrs_plan_create", "srsgpu_pdsch_dmrs_plan_create_ex", "srsgpu_pdsch_dmrs_plan_execute", "srsgpu_pdsch_dmrs_plan_destroy",
     "srsgpu_pdcch_plan_create", "srsgpu_pdcch_plan_execute", "srsgpu_pdcch_plan_destroy",
+    "srsgpu_pucch_detector_plan_create", "srsgpu_pucch_detector_plan_execute", "srsgpu_pucch_detector_plan_destroy",
     "srsgpu_debug_live_device_buffers",
 ]
 
@@ -1297,6 +1362,159 @@ class PdcchProcessor:
         torch.cuda.synchronize(dev)
         plan.close()
         return d_grids.cpu().numpy().view(np.uint32)
+
+
+@dataclass
+class PucchF0:
+    """pucch_detector::format0_configuration (pucch_detector.h) of one PDU: grid PRBs (the BWP start added), second_hop_prb
+    None without hopping, and `ports` the grid ports to read, in order."""
+    slot_index: int
+    starting_prb: int
+    start_symbol_index: int
+    nof_symbols: int
+    initial_cyclic_shift: int
+    n_id: int
+    nof_harq_ack: int
+    sr_opportunity: int
+    ports: Sequence[int] = (0,)
+    second_hop_prb: Optional[int] = None
+    numerology: int = 1
+    cp_extended: int = 0
+    grid_index: int = 0
+
+
+@dataclass
+class PucchF1:
+    """pucch_detector::format1_configuration of one resource with its multiplexed PUCCHs: entries = [(initial cyclic
+    shift, time-domain OCC, nof_harq_ack)], nof_harq_ack 0 meaning SR only. Grid ports 0..nof_rx_ports-1 are read."""
+    slot_index: int
+    starting_prb: int
+    start_symbol_index: int
+    nof_symbols: int
+    n_id: int
+    nof_rx_ports: int
+    entries: Sequence[tuple] = ()
+    second_hop_prb: Optional[int] = None
+    numerology: int = 1
+    cp_extended: int = 0
+    grid_index: int = 0
+
+
+def make_pucch_configs(f0_pdus: Sequence[PucchF0], f1_resources: Sequence[PucchF1]):
+    """The three C arrays of srsgpu_pucch_detector_plan_create; the entries of the resources follow one another."""
+    f0 = (PucchF0Config * max(len(f0_pdus), 1))()
+    for a, d in zip(f0, f0_pdus):
+        a.slot_index, a.numerology, a.cp_extended = d.slot_index, d.numerology, d.cp_extended
+        a.starting_prb = d.starting_prb
+        a.second_hop_prb = PUCCH_NO_HOP if d.second_hop_prb is None else d.second_hop_prb
+        a.start_symbol_index, a.nof_symbols, a.initial_cyclic_shift = d.start_symbol_index, d.nof_symbols, d.initial_cyclic_shift
+        a.nof_harq_ack, a.n_id, a.sr_opportunity = d.nof_harq_ack, d.n_id, d.sr_opportunity
+        a.nof_ports = len(d.ports)
+        for i, p in enumerate(list(d.ports)[:4]):
+            a.ports[i] = p
+        a.grid_index = d.grid_index
+    nof_entries = sum(len(r.entries) for r in f1_resources)
+    f1 = (PucchF1Resource * max(len(f1_resources), 1))()
+    ent = (PucchF1Entry * max(nof_entries, 1))()
+    first = 0
+    for a, r in zip(f1, f1_resources):
+        a.slot_index, a.numerology, a.cp_extended = r.slot_index, r.numerology, r.cp_extended
+        a.starting_prb = r.starting_prb
+        a.second_hop_prb = PUCCH_NO_HOP if r.second_hop_prb is None else r.second_hop_prb
+        a.start_symbol_index, a.nof_symbols, a.n_id, a.nof_rx_ports = r.start_symbol_index, r.nof_symbols, r.n_id, r.nof_rx_ports
+        a.grid_index, a.first_entry, a.nof_entries = r.grid_index, first, len(r.entries)
+        for i, (ics, occ, nof_harq_ack) in enumerate(r.entries):
+            e = ent[first + i]
+            e.initial_cyclic_shift, e.time_domain_occ, e.nof_harq_ack = ics, occ, nof_harq_ack
+        first += len(r.entries)
+    return f0, f1, ent, nof_entries
+
+
+class PucchDetectorPlan(_Handle):
+    """srsgpu_pucch_detector_plan: every Format 0 PDU and every Format 1 resource of a batch of slots detected in one
+    launch. Results: nof_f0 + (all entries) records of PUCCH_RESULT_DTYPE, the Format 0 PDUs first, then the entries of
+    the resources in order. Raises SrsGpuError on a refusal."""
+    _destroy = "srsgpu_pucch_detector_plan_destroy"
+
+    def __init__(self, ctx: Context, f0_pdus: Sequence[PucchF0], f1_resources: Sequence[PucchF1], grid_nof_prb: int,
+                 grid_nof_ports: int = 4, nof_grids: Optional[int] = None):
+        self.ctx = ctx
+        if nof_grids is None:
+            nof_grids = max([d.grid_index for d in list(f0_pdus) + list(f1_resources)], default=0) + 1
+        self.nof_grids, self.grid_nof_prb, self.grid_nof_ports = nof_grids, grid_nof_prb, grid_nof_ports
+        f0, f1, ent, nof_entries = make_pucch_configs(f0_pdus, f1_resources)
+        self.nof_f0, self.nof_entries = len(f0_pdus), nof_entries
+        self.nof_results = self.nof_f0 + nof_entries
+        h = ctypes.c_void_p()
+        _check(load_library().srsgpu_pucch_detector_plan_create(
+            ctx.handle, ctypes.cast(f0, ctypes.c_void_p), len(f0_pdus), ctypes.cast(f1, ctypes.c_void_p),
+            len(f1_resources), ctypes.cast(ent, ctypes.c_void_p), nof_entries, grid_nof_prb, grid_nof_ports, nof_grids,
+            ctypes.byref(h)))
+        self.handle = h
+
+    def execute(self, d_grids, d_results, stream=None):
+        """d_grids: (nof_grids, ports, 14, 12 PRBs) int32 / uint32 words (re | im << 16, bf16); d_results: device tensor
+        of at least 32 * nof_results bytes. Asynchronous on `stream`."""
+        _check(_lib.srsgpu_pucch_detector_plan_execute(self.handle, _dptr(d_grids), _dptr(d_results),
+                                                       _stream_handle(stream)))
+
+
+@dataclass
+class PucchResult:
+    """pucch_processor_result of one PUCCH: the message (sr and harq_ack bits, status True = uci_status::valid), the
+    detection metric (Format 1: over its threshold, as the reference reports it) and the linear channel state."""
+    sr: int
+    harq_ack: tuple
+    valid: bool
+    detection_metric: float
+    epre: float
+    rsrp: float
+    noise_var: float
+
+    @staticmethod
+    def _db(v):
+        return float(10.0 * np.log10(v)) if v > 0 else float("-inf") if v == 0 else float("nan")
+
+    @property
+    def epre_dB(self):
+        return self._db(self.epre)
+
+    @property
+    def rsrp_dB(self):
+        return self._db(self.rsrp)
+
+
+class PucchDetector:
+    """GPU counterpart of pucch_processor::process for Format 0 PDUs and Format 1 batches: process_batch(grids, f0_pdus,
+    f1_resources) returns ([PucchResult per PDU], [[PucchResult per entry] per resource]). grids: (nof_grids, ports,
+    14, 12 PRBs) uint32 (re | im << 16, bf16)."""
+
+    def __init__(self, ctx: Context, grid_nof_prb: int, grid_nof_ports: int = 4):
+        self.ctx, self.grid_nof_prb, self.grid_nof_ports = ctx, grid_nof_prb, grid_nof_ports
+
+    def raw_batch(self, grids: np.ndarray, f0_pdus: Sequence[PucchF0], f1_resources: Sequence[PucchF1]) -> np.ndarray:
+        """The results as a PUCCH_RESULT_DTYPE array."""
+        dev = torch.device("cuda", self.ctx.device)
+        plan = PucchDetectorPlan(self.ctx, f0_pdus, f1_resources, self.grid_nof_prb, self.grid_nof_ports, grids.shape[0])
+        d_grids = torch.from_numpy(np.ascontiguousarray(grids).view(np.int32)).to(dev)
+        d_results = torch.zeros(32 * max(plan.nof_results, 1), dtype=torch.uint8, device=dev)
+        plan.execute(d_grids, d_results)
+        torch.cuda.synchronize(dev)
+        plan.close()
+        return d_results.cpu().numpy().view(PUCCH_RESULT_DTYPE)[: plan.nof_results]
+
+    def process_batch(self, grids, f0_pdus: Sequence[PucchF0], f1_resources: Sequence[PucchF1]):
+        raw = self.raw_batch(grids, f0_pdus, f1_resources)
+
+        def one(r, nof_harq_ack):
+            return PucchResult(int(r["sr"]), tuple(int(b) for b in r["harq_ack"][:nof_harq_ack]), bool(r["status"]),
+                               float(r["detection_metric"]), float(r["epre"]), float(r["rsrp"]), float(r["noise_var"]))
+        f0_out = [one(raw[i], d.nof_harq_ack) for i, d in enumerate(f0_pdus)]
+        f1_out, at = [], len(f0_pdus)
+        for r in f1_resources:
+            f1_out.append([one(raw[at + i], e[2]) for i, e in enumerate(r.entries)])
+            at += len(r.entries)
+        return f0_out, f1_out
 
 
 @dataclass

@@ -532,6 +532,92 @@ int srsgpu_pucch_detector_plan_execute(const srsgpu_pucch_detector_plan* plan,
 void srsgpu_pucch_detector_plan_destroy(srsgpu_pucch_detector_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PRACH detector — replaces srsran::prach_detector::detect(const prach_buffer&, const configuration&)
+ * (include/srsran/phy/upper/channel_processors/prach_detector.h:78, the generic detector of
+ * lib/phy/upper/channel_processors/prach_detector_generic_impl.cpp:80 with the factory's IDFT sizes 1024 / 256) for
+ * every occasion of a batch in one launch: correlation with every root sequence on every port, the cyclic-shift
+ * windows with their noise estimates, and the decision per preamble.
+ *
+ * An occasion carries the physical values the detector computes with, not the PDU's indices: N_cs (what
+ * prach_cyclic_shifts_get returns for the zone), the Zadoff-Chu roots u of its root sequences (TS 38.211 Tables
+ * 6.3.3.1-3 / -4 applied to root_sequence_index + i), and the threshold and window margin of
+ * detail::get_threshold_and_margin. Unrestricted sets only. All powers are linear; delays are in samples of the IDFT:
+ * time_advance = delay_samples / (N x ra_scs), N = 1024 (long) or 256 (short).
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum {
+  SRSGPU_PRACH_FORMAT_0 = 0, SRSGPU_PRACH_FORMAT_1, SRSGPU_PRACH_FORMAT_2, SRSGPU_PRACH_FORMAT_3, SRSGPU_PRACH_FORMAT_A1,
+  SRSGPU_PRACH_FORMAT_A2, SRSGPU_PRACH_FORMAT_A3, SRSGPU_PRACH_FORMAT_B1, SRSGPU_PRACH_FORMAT_B4, SRSGPU_PRACH_FORMAT_C0,
+  SRSGPU_PRACH_FORMAT_C2, SRSGPU_PRACH_FORMAT_A1_B1, SRSGPU_PRACH_FORMAT_A2_B2, SRSGPU_PRACH_FORMAT_A3_B3
+};                                /* the order of prach_format_type */
+enum {
+  SRSGPU_PRACH_SCS_15 = 0, SRSGPU_PRACH_SCS_30, SRSGPU_PRACH_SCS_60, SRSGPU_PRACH_SCS_120, SRSGPU_PRACH_SCS_1_25,
+  SRSGPU_PRACH_SCS_5
+};                                /* the order of prach_subcarrier_spacing */
+#define SRSGPU_PRACH_MAX_PREAMBLES 64
+
+typedef struct {
+  uint8_t  format;               /* SRSGPU_PRACH_FORMAT_* */
+  uint8_t  ra_scs;               /* SRSGPU_PRACH_SCS_*: 1.25 kHz for Formats 0-2, 5 kHz for Format 3, 15-120 kHz for the short ones */
+  uint8_t  nof_rx_ports;         /* 1..4 */
+  uint8_t  combine_symbols;      /* 1: the symbols of a port are summed before the correlation (the factory's default) */
+  uint16_t n_cs;                 /* N_cs, 0..L_RA */
+  uint16_t nof_roots;            /* 64 when n_cs == 0, else ceil(64 / min(64, L_RA / n_cs)) */
+  uint32_t root_offset;          /* the roots u of the root sequences are roots[root_offset .. root_offset + nof_roots) */
+  uint8_t  start_preamble_index; /* monitored preambles [start, start + nof), within 0..64 */
+  uint8_t  nof_preamble_indices; /* 1..64 */
+  uint16_t win_margin;           /* > 0, samples of the IDFT */
+  float    threshold;            /* > 0 */
+  uint32_t sample_offset;        /* word of (port 0, symbol 0, RE 0) in the input */
+  uint32_t port_stride;          /* words between ports */
+  uint32_t symbol_stride;        /* words between symbols; the L_RA REs of a symbol are consecutive */
+  uint32_t result_index;         /* the occasion's srsgpu_prach_result; a permutation of 0..nof_occasions-1 over the plan */
+} srsgpu_prach_occasion;
+
+typedef struct {
+  uint32_t detected;             /* 1: peak > threshold and delay_samples < 0.8 x the maximum delay */
+  uint32_t delay_samples;        /* position of the first largest sample of the preamble's window */
+  float    metric;               /* peak / threshold (prach_detection_result::preamble_indication::detection_metric) */
+  float    peak;
+} srsgpu_prach_preamble;
+
+/** One per occasion. A preamble outside the monitored range is all zero; so is every preamble after an early stop. */
+typedef struct {
+  float                 rssi;        /* linear, with the reference's arithmetic (divided by L_RA twice) */
+  uint32_t              early_stop;  /* 1: the RSSI is no normal number and nothing was detected (detect()'s early return) */
+  uint32_t              reserved[2]; /* written as zero */
+  srsgpu_prach_preamble preambles[SRSGPU_PRACH_MAX_PREAMBLES];  /* by preamble index: the order of the indications */
+} srsgpu_prach_result;
+
+typedef struct srsgpu_prach_detector_plan srsgpu_prach_detector_plan;
+
+/** Refuses what detect() asserts on and what it leaves undefined: monitored preambles outside 0..64 or none, ports
+ *  outside 1..4, a format / SCS pair without preamble information, n_cs > L_RA, a root outside 1..L_RA-1, a wrong
+ *  nof_roots, threshold <= 0 or win_margin == 0, a window with its margins longer than the IDFT, samples outside the
+ *  input_words words of the input, and two occasions with one result. */
+int srsgpu_prach_detector_plan_create(srsgpu_context*              ctx,
+                                      const srsgpu_prach_occasion* occasions,
+                                      uint32_t                     nof_occasions,
+                                      const uint16_t*              roots,
+                                      uint32_t                     nof_roots,
+                                      uint64_t                     input_words,
+                                      srsgpu_prach_detector_plan** plan);
+
+/** Detects every occasion: reads d_input (uint32 per RE: re | im << 16, bf16, as prach_buffer holds them) and writes
+ *  every byte of the nof_occasions results. One launch for long and short occasions together, asynchronous on
+ *  `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_prach_detector_plan_execute(const srsgpu_prach_detector_plan* plan,
+                                       const uint32_t*                   d_input,
+                                       srsgpu_prach_result*              d_results,
+                                       void*                             stream);
+
+void srsgpu_prach_detector_plan_destroy(srsgpu_prach_detector_plan* plan);
+
+/** max_delay_samples of detect() (prach_detector_generic_impl.cpp:159) for a format, SCS and N_cs, in samples of the
+ *  IDFT: time_advance_max = 0.8 x it / (N x ra_scs). No device call. Fails for a format / SCS pair without preamble
+ *  information or N_cs > L_RA. */
+int srsgpu_prach_max_delay_samples(uint32_t format, uint32_t ra_scs, uint32_t n_cs, uint32_t* max_delay_samples);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

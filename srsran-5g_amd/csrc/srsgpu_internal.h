@@ -730,6 +730,17 @@ void launch_pucch_detector(const pucch_job*     d_jobs,
                            srsgpu_pucch_result* d_results,
                            hipStream_t          stream);
 
+/// PRACH detector (prach_detector.hip): one workgroup per job (prach_host.h: one root sequence of one occasion), the
+/// root sequences and the IDFT twiddles as (re, im) floats, and one srsgpu_prach_result per occasion.
+struct prach_job;
+void launch_prach_detector(const prach_job*     d_jobs,
+                           uint32_t             nof_jobs,
+                           const float*         d_roots,
+                           const float*         d_twiddles,
+                           const uint32_t*      d_input,
+                           srsgpu_prach_result* d_results,
+                           hipStream_t          stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

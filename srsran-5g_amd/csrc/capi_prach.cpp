@@ -11,7 +11,6 @@ using namespace srsgpu;
 static_assert(sizeof(srsgpu_prach_occasion) == 36, "srsgpu_prach_occasion layout (mirrored by srsgpu)");
 static_assert(sizeof(srsgpu_prach_preamble) == 16, "srsgpu_prach_preamble layout (mirrored by srsgpu)");
 static_assert(sizeof(srsgpu_prach_result) == 16 + 16 * SRSGPU_PRACH_MAX_PREAMBLES, "srsgpu_prach_result layout (mirrored by srsgpu)");
-static_assert(sizeof(prach_job) % 4 == 0, "the kernel copies the job by words");
 
 struct srsgpu_prach_detector_plan {
   srsgpu_context*          ctx = nullptr;

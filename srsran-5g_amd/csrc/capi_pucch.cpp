@@ -11,7 +11,6 @@ static_assert(sizeof(srsgpu_pucch_f0_config) == 24, "srsgpu_pucch_f0_config layo
 static_assert(sizeof(srsgpu_pucch_f1_resource) == 28, "srsgpu_pucch_f1_resource layout (mirrored by srsgpu)");
 static_assert(sizeof(srsgpu_pucch_f1_entry) == 4, "srsgpu_pucch_f1_entry layout (mirrored by srsgpu)");
 static_assert(sizeof(srsgpu_pucch_result) == 32, "srsgpu_pucch_result layout (mirrored by srsgpu)");
-static_assert(sizeof(pucch_job) % 4 == 0, "the kernel copies the job by words");
 
 struct srsgpu_pucch_detector_plan {
   srsgpu_context*          ctx = nullptr;

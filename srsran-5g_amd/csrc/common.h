@@ -22,24 +22,47 @@ __device__ __forceinline__ void static_for(F&& f)
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// Cross-lane reductions on DPP (VALU lane permutations: no LDS round trip, which __shfl_xor's ds_bpermute costs per
+// step). Within a 16-lane row: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror, after which every
+// lane of the row holds the row's result (each step pairs lanes symmetrically, so all lanes compute identical bits).
+// Across rows: row_bcast:15 into rows 1 and 3 (ROW_MASK 0xa; the 32-lane halves: lanes 31 / 63 hold them) and
+// row_bcast:31 into rows 2 and 3 (ROW_MASK 0xc; lane 63 holds the wave's), read back with readlane.
+constexpr int DPP_XOR1 = 0xb1, DPP_XOR2 = 0x4e, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
+constexpr int DPP_BCAST15 = 0x142, DPP_BCAST31 = 0x143;
+
+/// v permuted by CTRL within the rows of ROW_MASK; old in the other rows and where the source lane is out of range.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float dpp_f(float old, float v)
+{
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+}
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ int dpp_i(int old, int v)
+{
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ float readlane_f(float v, int lane)
+{
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
 /// One DPP step of a wave reduction: v ^ (v permuted by CTRL within the enabled rows; 0 elsewhere).
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_xor(uint32_t v)
 {
-  return v ^ static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, ROW_MASK, 0xf, false));
+  return v ^ static_cast<uint32_t>(dpp_i<CTRL, ROW_MASK>(0, static_cast<int>(v)));
 }
 
-/// XOR of v over the 64 lanes (all lanes must be active), returned to every lane. DPP steps: pairs, quads, half-rows,
-/// rows (quad_perm / mirrors), then row 0 -> 1 and 2 -> 3 (row_bcast:15) and rows 0-1 -> 2-3 (row_bcast:31): lane 63
-/// ends with the total. No LDS round trip (ds_bpermute) on the way.
+/// XOR of v over the 64 lanes (all lanes must be active), returned to every lane: the six steps above.
 __device__ __forceinline__ uint32_t wave_xor(uint32_t v)
 {
-  v = dpp_xor<0xb1>(v);          // quad_perm [1,0,3,2]
-  v = dpp_xor<0x4e>(v);          // quad_perm [2,3,0,1]
-  v = dpp_xor<0x141>(v);         // row_half_mirror
-  v = dpp_xor<0x140>(v);         // row_mirror
-  v = dpp_xor<0x142, 0xa>(v);    // row_bcast:15 into rows 1, 3
-  v = dpp_xor<0x143, 0xc>(v);    // row_bcast:31 into rows 2, 3
+  v = dpp_xor<DPP_XOR1>(v);
+  v = dpp_xor<DPP_XOR2>(v);
+  v = dpp_xor<DPP_HALF_MIRROR>(v);
+  v = dpp_xor<DPP_MIRROR>(v);
+  v = dpp_xor<DPP_BCAST15, 0xa>(v);
+  v = dpp_xor<DPP_BCAST31, 0xc>(v);
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
 }
 
@@ -47,18 +70,18 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v)
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_or(uint32_t v)
 {
-  return v | static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, ROW_MASK, 0xf, false));
+  return v | static_cast<uint32_t>(dpp_i<CTRL, ROW_MASK>(0, static_cast<int>(v)));
 }
 
 /// OR of v over the 64 lanes (all lanes active), returned to every lane; the steps of wave_xor.
 __device__ __forceinline__ uint32_t wave_or(uint32_t v)
 {
-  v = dpp_or<0xb1>(v);
-  v = dpp_or<0x4e>(v);
-  v = dpp_or<0x141>(v);
-  v = dpp_or<0x140>(v);
-  v = dpp_or<0x142, 0xa>(v);
-  v = dpp_or<0x143, 0xc>(v);
+  v = dpp_or<DPP_XOR1>(v);
+  v = dpp_or<DPP_XOR2>(v);
+  v = dpp_or<DPP_HALF_MIRROR>(v);
+  v = dpp_or<DPP_MIRROR>(v);
+  v = dpp_or<DPP_BCAST15, 0xa>(v);
+  v = dpp_or<DPP_BCAST31, 0xc>(v);
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
 }
 

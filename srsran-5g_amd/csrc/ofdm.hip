@@ -22,6 +22,7 @@
 // the M-point LDS transform of each scratch row k2 and writes output k2 + N2 k1 with the same fused last-pass work.
 // X[k2 + N2 k1] = sum_n1 W_M^(n1 k1) W_N^(n1 k2) sum_n2 x[n1 + M n2] W_N2^(n2 k2).
 #include <type_traits>
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 namespace srsgpu {
@@ -38,6 +39,7 @@ __device__ constexpr float kSin16[16] = {0.0f,  0.38268343236f,  0.70710678118f,
                                          0.0f,  -0.38268343236f, -0.70710678118f, -0.92387953251f,
                                          -1.0f, -0.92387953251f, -0.70710678118f, -0.38268343236f};
 
+// Complex arithmetic on float2, not signal_device.h's cpx: the 8-byte alignment is part of these kernels' LDS traffic.
 __device__ __forceinline__ float2 cadd(float2 a, float2 b)
 {
   return make_float2(a.x + b.x, a.y + b.y);
@@ -513,12 +515,6 @@ __device__ __forceinline__ void dft_any(float2* lds, const float2* __restrict__ 
   } else {
     dft_lds3<N, S>(lds, tw, src_first, dst_last);
   }
-}
-
-__device__ __forceinline__ uint32_t bf16_bits(float v)
-{
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
 /// One job of a launch resolved to its buffers: the grid row, the first sample of the symbol's cyclic prefix, the

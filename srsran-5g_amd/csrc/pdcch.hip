@@ -19,6 +19,7 @@
 //
 // Floating point follows the reference exactly: every product term is rounded separately (no contraction).
 #include "gold_device.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 #pragma clang fp contract(off)
@@ -27,12 +28,6 @@ namespace srsgpu {
 namespace {
 
 constexpr int PDCCH_THREADS = 256;
-
-__device__ __forceinline__ uint32_t pdcch_bf16_bits(float v)
-{
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 __global__ __launch_bounds__(PDCCH_THREADS) void pdcch_kernel(const pdcch_desc* __restrict__ descs,
                                                                const pdcch_code_desc* __restrict__ codes,
@@ -168,7 +163,7 @@ __global__ __launch_bounds__(PDCCH_THREADS) void pdcch_kernel(const pdcch_desc* 
       if (p < static_cast<int>(P)) {
         const float sr = re * wr[p] - im * wi[p];
         const float si = re * wi[p] + im * wr[p];
-        grids[e + static_cast<uint32_t>(p) * d.port_stride] = pdcch_bf16_bits(sr) | (pdcch_bf16_bits(si) << 16);
+        grids[e + static_cast<uint32_t>(p) * d.port_stride] = bf16_bits(sr) | (bf16_bits(si) << 16);
       }
     }
   }

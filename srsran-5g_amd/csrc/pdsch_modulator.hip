@@ -17,6 +17,7 @@
 // Floating point follows the reference exactly: every complex product term is rounded separately (no contraction),
 // layer terms are summed in layer order and the result is rounded to bf16 half-to-even.
 #include "gold_device.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 #pragma clang fp contract(off)
@@ -53,12 +54,6 @@ __global__ __launch_bounds__(MOD_THREADS) void gold_fill_kernel(const uint32_t* 
     const uint32_t w = (wstart != nullptr ? wstart[t] : 0u) + i;
     seq[offsets[t] + i] = gold_word(c_inits[t], w, w >> 6, x1, x2_jump, x2_lane);
   }
-}
-
-__device__ __forceinline__ uint32_t to_bf16_bits(float v)
-{
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
 /// Constellation point of a Qm-bit index on the TS 38.211 section 5.1 integer grid (Gray mapping; the amplitude is in
@@ -169,7 +164,7 @@ __device__ __forceinline__ void modulate_res(const mod_desc& d,
         }
         // (an unsigned 32-bit byte offset from the grid's SGPR base: saddr stores)
         *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(grids) + (e + static_cast<uint32_t>(p) * d.port_stride) * 4u) =
-            to_bf16_bits(sr) | (to_bf16_bits(si) << 16);
+            bf16_bits(sr) | (bf16_bits(si) << 16);
       }
     }
   }
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(MOD_THREADS) void pdsch_dmrs_kernel(const dmrs_job*
             si = si + (a * wi1 + b * wr1);
           }
           grids[jb.grid_base + static_cast<uint32_t>(p) * jb.port_stride + k] =
-              to_bf16_bits(sr) | (to_bf16_bits(si) << 16);
+              bf16_bits(sr) | (bf16_bits(si) << 16);
         }
       }
     }

@@ -17,6 +17,7 @@
 // group's first lane stores the preamble's slot. No atomics:
 // sequence s owns the slots of its preambles, sequence 0 also the header.
 #include "prach_host.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 namespace srsgpu {
@@ -24,28 +25,6 @@ namespace {
 
 constexpr uint32_t PRACH_THREADS = 256;
 constexpr uint32_t PRACH_WAVES   = PRACH_THREADS / 64;
-
-/// std::isnormal without the library: neither zero, subnormal, infinite nor NaN.
-__device__ __forceinline__ bool is_normal(float v)
-{
-  const uint32_t e = (__float_as_uint(v) >> 23) & 0xffu;
-  return e != 0u && e != 0xffu;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    v += __shfl_xor(v, m);
-  }
-  return v;
-}
-
-__device__ __forceinline__ prach_cf load_re(const uint32_t* __restrict__ input, uint32_t element)
-{
-  const uint32_t word = input[element];
-  return {__uint_as_float(word << 16), __uint_as_float(word & 0xffff0000u)};
-}
 
 __device__ __forceinline__ void store_preamble(srsgpu_prach_result* __restrict__ out, uint32_t preamble, uint32_t detected,
                                                uint32_t delay, float metric, float peak)
@@ -142,13 +121,13 @@ __device__ __forceinline__ void decide_preambles(const prach_job& job, const flo
 }
 
 __global__ __launch_bounds__(PRACH_THREADS) void prach_detector_kernel(const prach_job* __restrict__ jobs,
-                                                                        const prach_cf* __restrict__ roots,
-                                                                        const prach_cf* __restrict__ twiddles,
+                                                                        const cpx* __restrict__ roots,
+                                                                        const cpx* __restrict__ twiddles,
                                                                         const uint32_t* __restrict__ input,
                                                                         srsgpu_prach_result* __restrict__ results)
 {
-  __shared__ prach_cf  buf[2][PRACH_LONG_N];
-  __shared__ prach_cf  tw[PRACH_LONG_N];
+  __shared__ cpx       buf[2][PRACH_LONG_N];
+  __shared__ cpx       tw[PRACH_LONG_N];
   __shared__ float     mod[PRACH_LONG_N];
   __shared__ float     num[PRACH_LONG_N];
   __shared__ float     den[PRACH_LONG_N];
@@ -156,13 +135,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_detector_kernel(const pra
   __shared__ prach_job job;
 
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(jobs + blockIdx.x);
-    uint32_t*       dst = reinterpret_cast<uint32_t*>(&job);
-    for (uint32_t i = tid; i < sizeof(prach_job) / 4u; i += PRACH_THREADS) {
-      dst[i] = src[i];
-    }
-  }
+  copy_words(&job, jobs + blockIdx.x, tid, PRACH_THREADS);
   for (uint32_t i = tid; i < PRACH_LONG_N; i += PRACH_THREADS) {
     tw[i] = twiddles[i];
   }
@@ -178,8 +151,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_detector_kernel(const pra
 #pragma unroll 4
   for (uint32_t i = tid; i < P * per_port; i += PRACH_THREADS) {  // (several loads in flight per thread)
     const uint32_t p = i / per_port, r = i - p * per_port, s = r / L, n = r - s * L;
-    const prach_cf x = load_re(input, job.sample_offset + p * job.port_stride + s * job.symbol_stride + n);
-    power += x.re * x.re + x.im * x.im;
+    power += norm2(bf16c(input[job.sample_offset + p * job.port_stride + s * job.symbol_stride + n]));
   }
   power = wave_sum(power);
   if (lane == 0u) {
@@ -206,27 +178,27 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_detector_kernel(const pra
     num[i] = 0.0F;
     den[i] = 0.0F;
   }
-  const prach_cf* __restrict__ root = roots + job.root_row;
+  const cpx* __restrict__ root = roots + job.root_row;
   const uint32_t half = L / 2u;  // the IDFT input: its first L / 2 + 1 bins are the last ones of the product, :251-252
   const uint32_t nof_rounds = job.combine_symbols != 0u ? 1u : S;
   for (uint32_t p = 0; p < P; ++p) {
     for (uint32_t round = 0; round < nof_rounds; ++round) {
       const uint32_t base = job.sample_offset + p * job.port_stride + round * job.symbol_stride;
       for (uint32_t t = tid; t < N; t += PRACH_THREADS) {
-        prach_cf v = {0.0F, 0.0F};
+        cpx v = {0.0F, 0.0F};
         if (t <= half || t >= N - half) {
           const uint32_t n = t <= half ? half + t : t - (N - half);
-          prach_cf       x = load_re(input, base + n);
+          cpx            x = bf16c(input[base + n]);
           if (job.combine_symbols != 0u) {
 #pragma unroll 4
             for (uint32_t s = 1; s < S; ++s) {
-              const prach_cf y = load_re(input, base + s * job.symbol_stride + n);
-              x.re += y.re;
-              x.im += y.im;
+              const cpx y = bf16c(input[base + s * job.symbol_stride + n]);
+              x.x += y.x;
+              x.y += y.y;
             }
           }
-          const prach_cf r = root[n];
-          v                = {x.re * r.re + x.im * r.im, x.im * r.re - x.re * r.im};
+          const cpx r = root[n];  // x conj(r) written out: through cmulc this product contracts into other FMAs
+          v           = {x.x * r.x + x.y * r.y, x.y * r.x - x.x * r.y};
         }
         buf[0][t] = v;
       }
@@ -240,8 +212,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_detector_kernel(const pra
         src ^= 1u;
       }
       for (uint32_t t = tid; t < N; t += PRACH_THREADS) {
-        const prach_cf v = buf[src][t];
-        mod[t]           = (v.re * v.re + v.im * v.im) * job.mod_scale;
+        mod[t] = norm2(buf[src][t]) * job.mod_scale;
       }
       __syncthreads();
       switch (job.group_lanes) {
@@ -277,7 +248,7 @@ void launch_prach_detector(const prach_job*     d_jobs,
     return;
   }
   hipLaunchKernelGGL(prach_detector_kernel, dim3(nof_jobs), dim3(PRACH_THREADS), 0, stream, d_jobs,
-                     reinterpret_cast<const prach_cf*>(d_roots), reinterpret_cast<const prach_cf*>(d_twiddles), d_input,
+                     reinterpret_cast<const cpx*>(d_roots), reinterpret_cast<const cpx*>(d_twiddles), d_input,
                      d_results);
 }
 

@@ -8,6 +8,7 @@
 // lib/phy/upper/channel_processors/prach_detector_generic_impl.cpp:104-160 (derived quantities) / :268 (window start) /
 // :273-278 (reference interval), prach_generator_impl.cpp:97 / :212 (y_u, restated here as the DFT of x_u).
 #pragma once
+#include "cpx.h"
 #include "srsgpu_phy.h"
 #include <cstdint>
 #include <string>
@@ -80,29 +81,26 @@ std::vector<float> prach_root_sequence(uint32_t L, uint32_t u);
 /// exp(+j 2 pi k / N), k = 0..N-1, as (re, im) floats.
 std::vector<float> prach_twiddles(uint32_t N);
 
-struct prach_cf {
-  float re, im;
-};
-
 /// Butterfly j (0..N/4-1) of the radix-4 Stockham pass with sub-transform length ns (1, 4, 16, ...) of an inverse
-/// (exp(+j)) N-point transform: in -> out. tw is prach_twiddles(tw_n), tw_n a multiple of N.
-SRSGPU_HD void prach_stockham4(const prach_cf* in, prach_cf* out, const prach_cf* tw, uint32_t tw_n, uint32_t N, uint32_t ns,
+/// (exp(+j)) N-point transform: in -> out. tw is prach_twiddles(tw_n), tw_n a multiple of N. The arithmetic is written
+/// out: it compiles for the host too, where signal_device.h's helpers do not exist.
+SRSGPU_HD void prach_stockham4(const cpx* in, cpx* out, const cpx* tw, uint32_t tw_n, uint32_t N, uint32_t ns,
                                uint32_t j)
 {
   const uint32_t q = N >> 2, k = j & (ns - 1u), step = tw_n / (ns << 2);
-  prach_cf       v[4];
+  cpx            v[4];
 #pragma unroll
   for (uint32_t r = 0; r < 4u; ++r) {
-    const prach_cf x = in[j + r * q], w = tw[r * k * step];
-    v[r]             = {x.re * w.re - x.im * w.im, x.re * w.im + x.im * w.re};
+    const cpx x = in[j + r * q], w = tw[r * k * step];
+    v[r]        = {x.x * w.x - x.y * w.y, x.x * w.y + x.y * w.x};
   }
-  const prach_cf s02 = {v[0].re + v[2].re, v[0].im + v[2].im}, d02 = {v[0].re - v[2].re, v[0].im - v[2].im};
-  const prach_cf s13 = {v[1].re + v[3].re, v[1].im + v[3].im}, d13 = {v[1].re - v[3].re, v[1].im - v[3].im};
+  const cpx      s02 = {v[0].x + v[2].x, v[0].y + v[2].y}, d02 = {v[0].x - v[2].x, v[0].y - v[2].y};
+  const cpx      s13 = {v[1].x + v[3].x, v[1].y + v[3].y}, d13 = {v[1].x - v[3].x, v[1].y - v[3].y};
   const uint32_t at = ((j - k) << 2) + k;
-  out[at]           = {s02.re + s13.re, s02.im + s13.im};
-  out[at + ns]      = {d02.re - d13.im, d02.im + d13.re};  // + j d13
-  out[at + 2u * ns] = {s02.re - s13.re, s02.im - s13.im};
-  out[at + 3u * ns] = {d02.re + d13.im, d02.im - d13.re};  // - j d13
+  out[at]           = {s02.x + s13.x, s02.y + s13.y};
+  out[at + ns]      = {d02.x - d13.y, d02.y + d13.x};  // + j d13
+  out[at + 2u * ns] = {s02.x - s13.x, s02.y - s13.y};
+  out[at + 3u * ns] = {d02.x + d13.y, d02.y - d13.x};  // - j d13
 }
 
 } // namespace srsgpu

@@ -21,6 +21,7 @@
 // Format 0. Lane 8 c + row correlates row (symbol, port) with candidate c's sequence; three butterfly exchanges sum
 // the rows; every lane then walks the candidates in table order for the first strictly largest metric.
 #include "pucch_host.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 namespace srsgpu {
@@ -36,53 +37,14 @@ __constant__ float kCos24[24] = {1.0F,           0.96592582629F,  0.86602540378F
                                  -0.5F,          -0.25881904510F, 0.0F,            0.25881904510F,  0.5F,
                                  0.70710678119F, 0.86602540378F,  0.96592582629F};
 
-struct cf {
-  float re, im;
-};
-
 /// exp(j 2 pi k / 24), k in [0, 24).
-__device__ __forceinline__ cf root24(uint32_t k)
+__device__ __forceinline__ cpx root24(uint32_t k)
 {
   const uint32_t ks = k + 18u;
   return {kCos24[k], kCos24[ks >= 24u ? ks - 24u : ks]};
 }
 
-__device__ __forceinline__ cf mul(cf a, cf b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cf mul_conj(cf a, cf b) { return {a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im}; }
-__device__ __forceinline__ float norm2(cf a) { return a.re * a.re + a.im * a.im; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    v += __shfl_xor(v, m);
-  }
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    v = fmaxf(v, __shfl_xor(v, m));
-  }
-  return v;
-}
-
-/// std::isnormal without the library: neither zero, subnormal, infinite nor NaN.
-__device__ __forceinline__ bool is_normal(float v)
-{
-  const uint32_t e = (__float_as_uint(v) >> 23) & 0xffu;
-  return e != 0u && e != 0xffu;
-}
-
-__device__ __forceinline__ cf load_re(const uint32_t* __restrict__ grids, uint32_t element)
-{
-  const uint32_t word = grids[element];
-  return {__uint_as_float(word << 16), __uint_as_float(word & 0xffff0000u)};
-}
-
-__device__ __forceinline__ cf w_at(const float* __restrict__ w, uint32_t n, uint32_t i, uint32_t m)
+__device__ __forceinline__ cpx w_at(const float* __restrict__ w, uint32_t n, uint32_t i, uint32_t m)
 {
   const uint32_t at = 2u * ((n - 1u) * 49u + i * 7u + m);
   return {w[at], w[at + 1u]};
@@ -105,12 +67,12 @@ __device__ __forceinline__ void store_result(srsgpu_pucch_result* __restrict__ o
 }
 
 __device__ void detect_format0(const pucch_job& job, const uint32_t* __restrict__ grids,
-                               srsgpu_pucch_result* __restrict__ results, cf* lse)
+                               srsgpu_pucch_result* __restrict__ results, cpx* lse)
 {
   const uint32_t lane = threadIdx.x, P = job.nof_ports, rows = job.nof_symbols * P;
   for (uint32_t t = lane; t < rows * 12u; t += PUCCH_THREADS) {
     const uint32_t row = t / 12u, n = t - 12u * row, s = row / P, p = row - s * P;
-    lse[t] = load_re(grids, job.sym_base[s] + job.ports[p] * job.port_stride + n);
+    lse[t] = bf16c(grids[job.sym_base[s] + job.ports[p] * job.port_stride + n]);
   }
   __syncthreads();
   const uint32_t c = lane >> 3, row = lane & 7u;
@@ -120,17 +82,17 @@ __device__ void detect_format0(const pucch_job& job, const uint32_t* __restrict_
     const uint32_t s = row / P;
     uint32_t       alpha = job.alpha[s] + job.m_cs[c];
     alpha                = alpha >= 12u ? alpha - 12u : alpha;
-    cf    corr = {0.0F, 0.0F};
+    cpx   corr = {0.0F, 0.0F};
     float pw   = 0.0F;
     uint32_t k = 0;  // 2 alpha n mod 24
 #pragma unroll
     for (uint32_t n = 0; n < 12u; ++n) {
-      const cf       x  = lse[row * 12u + n];
+      const cpx      x  = lse[row * 12u + n];
       const uint32_t kk = job.phi3[n] + k;
-      const cf       r  = root24(kk >= 24u ? kk - 24u : kk);
-      const cf       y  = mul_conj(x, r);
-      corr.re += y.re;
-      corr.im += y.im;
+      const cpx      r  = root24(kk >= 24u ? kk - 24u : kk);
+      const cpx      y  = cmulc(x, r);
+      corr.x += y.x;
+      corr.y += y.y;
       pw += norm2(x);
       k += 2u * alpha;
       k = k >= 24u ? k - 24u : k;
@@ -167,8 +129,8 @@ __device__ void detect_format0(const pucch_job& job, const uint32_t* __restrict_
 }
 
 __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict__ entries, const float* __restrict__ w,
-                               const uint32_t* __restrict__ grids, srsgpu_pucch_result* __restrict__ results, cf* lse,
-                               cf* dft, cf* rebuilt, cf* ch, float (*met)[7][12][4])
+                               const uint32_t* __restrict__ grids, srsgpu_pucch_result* __restrict__ results, cpx* lse,
+                               cpx* dft, cpx* rebuilt, cpx* ch, float (*met)[7][12][4])
 {
   const uint32_t lane = threadIdx.x, P = job.nof_ports, S = job.nof_symbols, items = S * P * 12u;
   const uint32_t dmrs_mask = job.dmrs_mask;
@@ -177,23 +139,23 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
   float epre = 0.0F;
   for (uint32_t t = lane; t < items; t += PUCCH_THREADS) {
     const uint32_t row = t / 12u, n = t - 12u * row, s = row / P, p = row - s * P;
-    const cf       x = load_re(grids, job.sym_base[s] + job.ports[p] * job.port_stride + n);
+    const cpx      x = bf16c(grids[job.sym_base[s] + job.ports[p] * job.port_stride + n]);
     epre += norm2(x);
     const uint32_t k = (job.phi3[n] + 2u * job.alpha[s] * n) % 24u;
-    lse[t]           = mul_conj(x, root24(k));
+    lse[t]           = cmulc(x, root24(k));
     rebuilt[t]       = {0.0F, 0.0F};
   }
   __syncthreads();
   // 12-point DFT of every row: bin k is the despread signal of initial cyclic shift k.
   for (uint32_t t = lane; t < items; t += PUCCH_THREADS) {
     const uint32_t row = t / 12u, k = t - 12u * row;
-    cf             acc = {0.0F, 0.0F};
+    cpx            acc = {0.0F, 0.0F};
     uint32_t       q = 0;  // n k mod 12
 #pragma unroll
     for (uint32_t n = 0; n < 12u; ++n) {
-      const cf y = mul(lse[row * 12u + n], root24(q == 0u ? 0u : 24u - 2u * q));
-      acc.re += y.re;
-      acc.im += y.im;
+      const cpx y = cmul(lse[row * 12u + n], root24(q == 0u ? 0u : 24u - 2u * q));
+      acc.x += y.x;
+      acc.y += y.y;
       q += k;
       q = q >= 12u ? q - 12u : q;
     }
@@ -216,33 +178,33 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
         continue;
       }
       // Despread in time: data and DM-RS symbols separately, with w* / sqrt(n).
-      cf data = {0.0F, 0.0F}, dmrs = {0.0F, 0.0F};
+      cpx data = {0.0F, 0.0F}, dmrs = {0.0F, 0.0F};
       if (active) {
         uint32_t id = 0, im = 0;
         for (uint32_t s = first; s < end; ++s) {
-          const cf   v       = dft[(s * P + p) * 12u + k];
+          const cpx  v       = dft[(s * P + p) * 12u + k];
           const bool is_dmrs = ((dmrs_mask >> s) & 1u) != 0u;
-          const cf   ws      = is_dmrs ? w_at(w, nm, occ, im) : w_at(w, nd, occ, id);
-          const cf   y       = mul_conj(v, ws);
+          const cpx  ws      = is_dmrs ? w_at(w, nm, occ, im) : w_at(w, nd, occ, id);
+          const cpx  y       = cmulc(v, ws);
           if (is_dmrs) {
-            dmrs.re += y.re, dmrs.im += y.im, ++im;
+            dmrs.x += y.x, dmrs.y += y.y, ++im;
           } else {
-            data.re += y.re, data.im += y.im, ++id;
+            data.x += y.x, data.y += y.y, ++id;
           }
         }
-        data = {data.re * inv_sqrt_nd, data.im * inv_sqrt_nd};
-        dmrs = {dmrs.re * inv_sqrt_nm, dmrs.im * inv_sqrt_nm};
+        data = {data.x * inv_sqrt_nd, data.y * inv_sqrt_nd};
+        dmrs = {dmrs.x * inv_sqrt_nm, dmrs.y * inv_sqrt_nm};
       }
       // Main and cross contributions and the channel energy, summed over the ports of a shift.
       const float est_norm = 1.0F / (sqrtf(static_cast<float>(nm)) * 12.0F);
-      cf          chv   = {dmrs.re * est_norm, dmrs.im * est_norm};
-      cf          cross = mul_conj(dmrs, data);
+      cpx         chv   = {dmrs.x * est_norm, dmrs.y * est_norm};
+      cpx         cross = cmulc(dmrs, data);
       float       main_c = norm2(data) + norm2(dmrs), energy = norm2(chv);
 #pragma unroll
       for (int m = 1; m <= 2; m <<= 1) {
         main_c += __shfl_xor(main_c, m);
-        cross.re += __shfl_xor(cross.re, m);
-        cross.im += __shfl_xor(cross.im, m);
+        cross.x += __shfl_xor(cross.x, m);
+        cross.y += __shfl_xor(cross.y, m);
         energy += __shfl_xor(energy, m);
       }
       const float scale = 1.0F / static_cast<float>(12u * (nm + nd));
@@ -252,11 +214,11 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
         chv = {0.0F, 0.0F};
       }
       if (lane < 48u) {
-        ch[p * 12u + k] = active ? chv : cf{0.0F, 0.0F};
+        ch[p * 12u + k] = active ? chv : cpx{0.0F, 0.0F};
         if (p == 0u) {
           met[hop][occ][k][0] = main_c * scale;
-          met[hop][occ][k][1] = cross.re * scale;
-          met[hop][occ][k][2] = cross.im * scale;
+          met[hop][occ][k][1] = cross.x * scale;
+          met[hop][occ][k][2] = cross.y * scale;
           met[hop][occ][k][3] = energy * (1.0F / static_cast<float>(P));
         }
       }
@@ -267,20 +229,20 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
         if (((dmrs_mask >> s) & 1u) == 0u) {
           continue;
         }
-        cf       acc = {0.0F, 0.0F};
+        cpx      acc = {0.0F, 0.0F};
         uint32_t q = 0;  // n k mod 12
 #pragma unroll
         for (uint32_t kk = 0; kk < 12u; ++kk) {
-          const cf y = mul(ch[pp * 12u + kk], root24(2u * q));
-          acc.re += y.re;
-          acc.im += y.im;
+          const cpx y = cmul(ch[pp * 12u + kk], root24(2u * q));
+          acc.x += y.x;
+          acc.y += y.y;
           q += n;
           q = q >= 12u ? q - 12u : q;
         }
         const uint32_t im = __popc(dmrs_mask & ((1u << s) - 1u) & ~((1u << first) - 1u));
-        const cf       y  = mul(acc, w_at(w, nm, occ, im));
-        rebuilt[t].re += y.re;
-        rebuilt[t].im += y.im;
+        const cpx      y  = cmul(acc, w_at(w, nm, occ, im));
+        rebuilt[t].x += y.x;
+        rebuilt[t].y += y.y;
       }
       __syncthreads();
     }
@@ -289,7 +251,7 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
     for (uint32_t t = lane + first * P * 12u; t < end * P * 12u; t += PUCCH_THREADS) {
       const uint32_t s = t / (12u * P);
       if (((dmrs_mask >> s) & 1u) != 0u) {
-        const cf d = {lse[t].re - rebuilt[t].re, lse[t].im - rebuilt[t].im};
+        const cpx d = {lse[t].x - rebuilt[t].x, lse[t].y - rebuilt[t].y};
         acc += norm2(d);
       }
     }
@@ -302,16 +264,16 @@ __device__ void detect_format1(const pucch_job& job, const uint32_t* __restrict_
     const uint32_t word = entries[job.first_entry + e];
     const uint32_t ics = word & 0xffu, occ = (word >> 8) & 0xffu, nof_bits = (word >> 16) & 0xffu;
     float          main_c = met[0][occ][ics][0], rsrp = met[0][occ][ics][3];
-    cf             cross = {met[0][occ][ics][1], met[0][occ][ics][2]};
+    cpx            cross = {met[0][occ][ics][1], met[0][occ][ics][2]};
     if (job.nof_hops == 2) {
       main_c += met[1][occ][ics][0];
-      cross.re += met[1][occ][ics][1];
-      cross.im += met[1][occ][ics][2];
+      cross.x += met[1][occ][ics][1];
+      cross.y += met[1][occ][ics][2];
       rsrp = (rsrp * n0 + met[1][occ][ics][3] * n1) / static_cast<float>(noise_samples[0] + noise_samples[1]);
     }
     // detect_symbol: the BPSK or QPSK symbol with the largest real part of symbol x cross term.
     const float a  = 0.70710678118654752440F;
-    const float m1 = a * cross.re - a * cross.im, m2 = a * cross.re + a * cross.im;
+    const float m1 = a * cross.x - a * cross.y, m2 = a * cross.x + a * cross.y;
     uint32_t    b0 = 0, b1 = 0;
     float       detected = m1;
     if (nof_bits == 2u && fabsf(m2) > fabsf(m1)) {
@@ -337,19 +299,15 @@ __global__ __launch_bounds__(PUCCH_THREADS) void pucch_detector_kernel(const puc
                                                                         const uint32_t* __restrict__ grids,
                                                                         srsgpu_pucch_result* __restrict__ results)
 {
-  __shared__ cf    lse[PUCCH_MAX_ROWS * 12];
-  __shared__ cf    dft[PUCCH_MAX_ROWS * 12];
-  __shared__ cf    rebuilt[PUCCH_MAX_ROWS * 12];
-  __shared__ cf    ch[48];
+  __shared__ cpx   lse[PUCCH_MAX_ROWS * 12];
+  __shared__ cpx   dft[PUCCH_MAX_ROWS * 12];
+  __shared__ cpx   rebuilt[PUCCH_MAX_ROWS * 12];
+  __shared__ cpx   ch[48];
   __shared__ float met[2][7][12][4];
   __shared__ pucch_job job;
 
   // The descriptor goes to LDS once: every lane indexes its byte tables.
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(jobs + blockIdx.x);
-  uint32_t*       dst = reinterpret_cast<uint32_t*>(&job);
-  for (uint32_t i = threadIdx.x; i < sizeof(pucch_job) / 4u; i += PUCCH_THREADS) {
-    dst[i] = src[i];
-  }
+  copy_words(&job, jobs + blockIdx.x, threadIdx.x, PUCCH_THREADS);
   __syncthreads();
   if (job.kind == 0u) {
     detect_format0(job, grids, results, lse);

@@ -22,8 +22,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
 #include "gold_device.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 namespace srsgpu {
@@ -56,42 +56,8 @@ __device__ uint64_t g_chest_prof[CHEST_PROF_JOBS * CHEST_PROF_SLOTS];
 constexpr int CHEST_THREADS = 64;  // one wavefront per job (multi-wave workgroups for large allocations: T)
 constexpr int CHEST_VP      = 12;  // MAX_V_PILOTS
 
-struct cpx {
-  float x, y;
-};
-__device__ __forceinline__ cpx bf16c(uint32_t u)
-{
-  return {__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
-}
-__device__ __forceinline__ uint32_t bf16_bits(float v)
-{
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t to_bf16c(cpx v)
-{
-  return bf16_bits(v.x) | (bf16_bits(v.y) << 16);
-}
-
-// Cross-lane reductions on DPP (VALU lane permutations: no LDS round trip, which __shfl_xor's ds_bpermute costs per
-// step). Within a 16-lane row: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror, after which every
-// lane of the row holds the row's result (each step pairs lanes symmetrically, so all lanes compute identical bits).
-// Across rows: row_bcast:15 into rows 1 and 3 (the 32-lane halves: lanes 31 / 63 hold them) and row_bcast:31 into
-// rows 2 and 3 (lane 63 holds the wave's), read back with readlane.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_f(float old, float v)
-{
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int dpp_i(int old, int v)
-{
-  return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false);
-}
-constexpr int DPP_XOR1 = 0xb1, DPP_XOR2 = 0x4e, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
-constexpr int DPP_BCAST15 = 0x142, DPP_BCAST31 = 0x143;
-
+// The estimator's reductions run on DPP (common.h: the steps, their names and dpp_f / dpp_i / readlane_f). They add in
+// another order than signal_device.h's butterfly wave_sum, so the float sums differ in the last bit: these stay here.
 __device__ __forceinline__ float row_sum(float v)
 {
   v += dpp_f<DPP_XOR1>(0.f, v);
@@ -101,13 +67,8 @@ __device__ __forceinline__ float row_sum(float v)
   return v;
 }
 
-__device__ __forceinline__ float readlane_f(float v, int lane)
-{
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 /// Sum over the wavefront (every lane gets the result).
-__device__ __forceinline__ float wave_sum(float v)
+__device__ __forceinline__ float wave_sum_dpp(float v)
 {
   v = row_sum(v);
   v += dpp_f<DPP_BCAST15, 0xa>(0.f, v);
@@ -119,7 +80,7 @@ __device__ __forceinline__ float wave_sum(float v)
 template <int T>
 __device__ __forceinline__ float block_sum(float v, float* red)
 {
-  v = wave_sum(v);
+  v = wave_sum_dpp(v);
   if constexpr (T > 64) {
     __syncthreads();  // red may still be read by a previous reduction
     if ((threadIdx.x & 63u) == 0) {
@@ -141,7 +102,7 @@ __device__ __forceinline__ float sub_sum(float v)
 {
   static_assert(TS == 16 || TS == 32 || TS == 64, "row, half-wave or wave");
   if constexpr (TS == 64) {
-    return wave_sum(v);
+    return wave_sum_dpp(v);
   } else {
     v = row_sum(v);
     if constexpr (TS == 32) {
@@ -174,7 +135,7 @@ __device__ __forceinline__ void job_sum_n(float (&v)[K], float* red)
     if constexpr (TS < 64) {
       v[k] = sub_sum<TS>(v[k]);
     } else {
-      v[k] = wave_sum(v[k]);
+      v[k] = wave_sum_dpp(v[k]);
     }
   }
   if constexpr (TS >= 64 && T > 64) {
@@ -282,11 +243,6 @@ __device__ __forceinline__ void virtual_pilots(cpx* E, int N, int nv, int sub)
 }
 
 constexpr float CHEST_TWOPI = 6.283185307f;  // TWOPI (srsran/support/math_utils.h)
-
-__device__ __forceinline__ cpx cmul(cpx a, cpx b)
-{
-  return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
 
 /// std::polar(1.0F, theta) in float.
 __device__ __forceinline__ cpx polar1(float theta)
@@ -534,6 +490,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(CHEST_WAVES_P
   // (A/B on MI355X: chest stage 32.6 -> 28.9 us per 16-slot step).
   __shared__ chest_job sjob[JPW];
   {
+    // The word copy written out, not signal_device.h's copy_words: with the helper the estimator compiles differently.
     static_assert(sizeof(chest_job) % 4 == 0, "word copy");
     const uint32_t* src = reinterpret_cast<const uint32_t*>(jobs + job);
     uint32_t*       dst = reinterpret_cast<uint32_t*>(&sjob[slot]);

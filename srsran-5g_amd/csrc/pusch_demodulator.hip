@@ -14,8 +14,8 @@
 // contiguous LLR range with dword stores. HBM-bound: (P + L P) x 4 B in and L Qm B out per RE.
 #include <cstdlib>
 
-#include "common.h"
 #include "gold_device.h"
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 
 // Contraction (FMA) is allowed in the equalizer; the demapper keeps the reference's separately rounded mul / add.
@@ -27,25 +27,10 @@ namespace {
 constexpr int DEMOD_THREADS = 256;
 constexpr int DEMOD_OUT_BYTES = DEMOD_CHUNK_WORDS * 32 + 64;
 
-struct cpx {
-  float x, y;
-};
+// cpx, bf16c, to_bf16c, cmul and cmulc come from signal_device.h; only the equalizers here use the rest.
 __device__ __forceinline__ cpx cmk(float x, float y)
 {
   return {x, y};
-}
-__device__ __forceinline__ cpx bf16c(uint32_t u)
-{
-  return {__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
-}
-__device__ __forceinline__ cpx cmul(cpx a, cpx b)
-{
-  return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-/// a * conj(b)
-__device__ __forceinline__ cpx cmulc(cpx a, cpx b)
-{
-  return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y};
 }
 __device__ __forceinline__ cpx cadd(cpx a, cpx b)
 {
@@ -59,6 +44,7 @@ __device__ __forceinline__ cpx cscale(cpx a, float s)
 {
   return {a.x * s, a.y * s};
 }
+/// The builtin, not signal_device.h's is_normal: the exponent test gives the same answers but compiles differently here.
 __device__ __forceinline__ bool isnormal_f(float v)
 {
   return __builtin_isnormal(v);
@@ -316,13 +302,6 @@ struct lane_stats {
     n += 1.f;
   }
 };
-
-/// Round-to-nearest-even float -> bf16 pair (adt/bf16.h), the estimator's storage rounding.
-__device__ __forceinline__ uint32_t to_bf16c(cpx v)
-{
-  const uint32_t a = __float_as_uint(v.x), b = __float_as_uint(v.y);
-  return ((a + 0x7fffu + ((a >> 16) & 1u)) >> 16) | (((b + 0x7fffu + ((b >> 16) & 1u)) >> 16) << 16);
-}
 
 /// Stages the chunk's descrambling words (and the first word of the next chunk) and, for 64/256QAM, the demapper
 /// tables in LDS. The caller synchronises.

@@ -22,6 +22,7 @@
 // order, and the high bits of k select one of 2^(A-6) sign masks (XORs of words 6..10) applied before it. Each half of
 // the wave transforms one mask at a time, five butterfly stages through cross-lane shuffles, no LDS. Byte traffic: E
 // LLR bytes read per field, three bytes written.
+#include "signal_device.h"
 #include "srsgpu_internal.h"
 #include "uci_basis_words.h"
 
@@ -69,25 +70,10 @@ static_assert(uci_hadamard_index_is_permutation(), "basis words 1..5 must take 3
 constexpr uint32_t kUciPositionPlanes[5] = {uci_position_plane(0), uci_position_plane(1), uci_position_plane(2),
                                             uci_position_plane(3), uci_position_plane(4)};
 
+/// min(max()), not common.h's clamp_i: the ternary form gives the same integers but compiles differently here.
 __device__ inline int clamp_int(int x, int lo, int hi)
 {
   return min(max(x, lo), hi);
-}
-
-__device__ inline int wave_sum(int v)
-{
-  for (int o = 32; o > 0; o >>= 1) {
-    v += __shfl_xor(v, o);
-  }
-  return v;
-}
-
-__device__ inline int wave_max(int v)
-{
-  for (int o = 32; o > 0; o >>= 1) {
-    v = max(v, __shfl_xor(v, o));
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(UCI_THREADS) void uci_decoder_kernel(const uci_field_desc* __restrict__ descs,

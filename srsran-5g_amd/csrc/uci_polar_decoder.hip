@@ -96,7 +96,8 @@ __device__ inline uint32_t pack4(int a, int b, int c, int d)
          ((static_cast<uint32_t>(c) & 0xffu) << 16) | (static_cast<uint32_t>(d) << 24);
 }
 
-__device__ inline uint32_t wave_xor(uint32_t v)
+// The shuffle form, not common.h's DPP wave_xor: the same integers but other code, whose speed here is not measured.
+__device__ inline uint32_t wave_xor_shfl(uint32_t v)
 {
   for (int o = 32; o > 0; o >>= 1) {
     v ^= static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o));
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(POLAR_THREADS) void uci_polar_decoder_kernel(
     const uint32_t q = info[k];
     crc ^= ((s_u[wave][q >> 5] >> (q & 31u)) & 1u) != 0 ? weights[k] : 0u;
   }
-  const bool ok = wave_xor(crc) == 0;
+  const bool ok = wave_xor_shfl(crc) == 0;
 
   // Message bits of this codeblock (uci_decoder_impl.cpp:113): K-set bits [filler, K - L).
   const uint32_t A      = fd.nof_bits;

@@ -48,17 +48,17 @@ T take(const std::vector<char>& raw, size_t& pos)
 void check_stockham(uint32_t N)
 {
   const std::vector<float> twf = prach_twiddles(PRACH_LONG_N);
-  std::vector<prach_cf>    tw(PRACH_LONG_N), a(N), b(N);
+  std::vector<cpx>         tw(PRACH_LONG_N), a(N), b(N);
   std::memcpy(static_cast<void*>(tw.data()), twf.data(), twf.size() * sizeof(float));
   uint32_t state = 12345u + N;
-  for (prach_cf& v : a) {
+  for (cpx& v : a) {
     state = state * 1664525u + 1013904223u;
-    v.re  = static_cast<float>(static_cast<int32_t>(state >> 8) % 2001 - 1000) / 1000.0F;
+    v.x   = static_cast<float>(static_cast<int32_t>(state >> 8) % 2001 - 1000) / 1000.0F;
     state = state * 1664525u + 1013904223u;
-    v.im  = static_cast<float>(static_cast<int32_t>(state >> 8) % 2001 - 1000) / 1000.0F;
+    v.y   = static_cast<float>(static_cast<int32_t>(state >> 8) % 2001 - 1000) / 1000.0F;
   }
-  const std::vector<prach_cf> x = a;
-  prach_cf *src = a.data(), *dst = b.data();
+  const std::vector<cpx> x = a;
+  cpx *src = a.data(), *dst = b.data();
   for (uint32_t ns = 1; ns < N; ns <<= 2) {
     for (uint32_t j = 0; j < N / 4; ++j) {
       prach_stockham4(src, dst, tw.data(), PRACH_LONG_N, N, ns, j);
@@ -70,10 +70,10 @@ void check_stockham(uint32_t N)
     double re = 0.0, im = 0.0;
     for (uint32_t f = 0; f < N; ++f) {
       const double ang = 2.0 * 3.14159265358979323846 * static_cast<double>((static_cast<uint64_t>(f) * m) % N) / N;
-      re += x[f].re * std::cos(ang) - x[f].im * std::sin(ang);
-      im += x[f].re * std::sin(ang) + x[f].im * std::cos(ang);
+      re += x[f].x * std::cos(ang) - x[f].y * std::sin(ang);
+      im += x[f].x * std::sin(ang) + x[f].y * std::cos(ang);
     }
-    worst   = std::max(worst, std::hypot(src[m].re - re, src[m].im - im));
+    worst   = std::max(worst, std::hypot(src[m].x - re, src[m].y - im));
     largest = std::max(largest, std::hypot(re, im));
   }
   CHECK(worst < 1e-5 * largest, "%u-point inverse transform deviates by %g of %g", N, worst, largest);

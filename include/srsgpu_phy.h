@@ -441,6 +441,116 @@ int srsgpu_pdcch_plan_execute(const srsgpu_pdcch_plan* plan,
 void srsgpu_pdcch_plan_destroy(srsgpu_pdcch_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * SS/PBCH block — replaces srsran::ssb_processor::process(resource_grid_writer& grid, const pdu_t& pdu)
+ * (include/srsran/phy/upper/channel_processors/ssb/ssb_processor.h, lib/phy/upper/channel_processors/ssb/
+ * ssb_processor_impl.cpp:29) for every block of a batch of slots, in one launch: PBCH payload generation, first
+ * scrambling, CRC24C, polar encoding and rate matching (pbch_encoder_impl.cpp:41-:163), second scrambling, QPSK and RE
+ * mapping (pbch_modulator_impl.cpp:30-:91), the PBCH DM-RS (signal_processors/dmrs_pbch_processor_impl.cpp:29-:85), the
+ * PSS and the SSS (pss_processor_impl.cpp, sss_processor_impl.cpp), on every port of a port list without precoding,
+ * into bf16 grids of the PDSCH modulator's layout. Bit-exact with the reference. Only the REs the reference writes are
+ * written: symbol l_start outside the PSS and the gaps beside the SSS stay as they are.
+ *
+ * l_start and k_start are derived at plan creation (include/srsran/ran/ssb/ssb_mapping.h:42 / :116). pss_amplitude is
+ * linear, as in the PDCCH plan: the caller converts beta_pss. The 24 BCH payload bits and the SFN's four LSBs are read
+ * from device memory at execution, four bytes per block: bytes 0-2 the payload, MSB first, byte 3 sfn & 15.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint32_t phys_cell_id;      /* 0..1007 */
+  uint32_t ssb_idx;           /* < L_max */
+  uint32_t L_max;             /* 4, 8 or 64 */
+  uint32_t pattern_case;      /* ssb_pattern_case: 0..4 = A..E */
+  uint32_t common_scs;        /* subCarrierSpacingCommon as a numerology: 0..2 for cases A-C, 2..4 for D and E */
+  uint32_t offset_to_pointA;  /* 0..2199, in RBs of 15 kHz (A-C) or 60 kHz (D, E) */
+  uint32_t subcarrier_offset; /* k_SSB: 0..23 (A-C) or 0..11 (D, E) */
+  uint32_t slot_index;        /* pdu_t::slot.hrf_slot_index(): the slot within the half frame, block SCS */
+  uint32_t hrf;               /* pdu_t::slot.is_odd_hrf() */
+  float    pss_amplitude;     /* linear; finite */
+  uint32_t nof_ports;         /* 1..4 */
+  uint8_t  ports[4];          /* grid ports the block is written to, each once */
+  uint32_t grid_index;        /* resource grid (slot) the block is mapped into, < nof_grids */
+  uint32_t payload_offset;    /* byte offset of the block's four bytes in d_payloads */
+  uint32_t reserved[2];
+} srsgpu_ssb_config;
+
+typedef struct srsgpu_ssb_plan srsgpu_ssb_plan;
+
+/** Refuses, with the reference's reason as the message where it has one, a slot that is not the block's, the offsets
+ *  and SCS combinations ssb_get_k_first asserts on, ssb_idx >= L_max, L_max outside {4, 8, 64}, a block outside the grid
+ *  in subcarriers or symbols, a port outside the grid or listed twice, two blocks that write the same REs (one launch
+ *  gives them no order), and grids past 2^32 words. */
+int srsgpu_ssb_plan_create(srsgpu_context*          ctx,
+                           const srsgpu_ssb_config* cfgs,
+                           uint32_t                 nof_blocks,
+                           uint32_t                 grid_nof_prb,
+                           uint32_t                 grid_nof_ports,
+                           uint32_t                 nof_grids,
+                           srsgpu_ssb_plan**        plan);
+
+/** Encodes and maps every planned block: reads the payloads and SFN bits from d_payloads (payload_bytes bytes, device
+ *  memory, so a captured graph carries a new MIB or SFN on every replay) and writes d_grids (uint32 per RE:
+ *  re | im << 16). One launch, asynchronous on `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_ssb_plan_execute(const srsgpu_ssb_plan* plan,
+                            const uint8_t*         d_payloads,
+                            uint64_t               payload_bytes,
+                            uint32_t*              d_grids,
+                            void*                  stream);
+
+void srsgpu_ssb_plan_destroy(srsgpu_ssb_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * NZP-CSI-RS — replaces srsran::nzp_csi_rs_generator::map(resource_grid_writer& grid, const config_t& config)
+ * (include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h, lib/phy/upper/signal_processors/
+ * nzp_csi_rs_generator_impl.cpp:175) for every signal of a batch of slots, in one launch: the RE positions of TS 38.211
+ * Table 7.4.1.5.3-1 (lib/ran/csi_rs/csi_rs_pattern.cpp, at plan creation), the sequence (:111, c_init :123, the skipped
+ * elements :72, the length :142), the w_f cover (:291) and the precoding of each CDM group onto all ports, into bf16
+ * grids of the PDSCH modulator's layout. Bit-exact with the reference. Only the words the reference writes are written:
+ * with the identity matrix these include zeros on the ports of the other CDM group (rows 4 and 5).
+ *
+ * Rows 1-5 (1, 2 or 4 ports; no CDM or FD-CDM2). Rows 6-12 need 8-16 grid ports and are refused, rows 13-18 the
+ * reference refuses itself. Precoding is one PRG: a ports x ports matrix (the same mapper reason as the PDCCH plan).
+ * amplitude is config_t::amplitude, linear. Extended CP changes c_init and the l_0 range; the grid keeps 14 symbols.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint32_t slot_index;        /* n_slot within the frame (config_t::slot) */
+  uint32_t cp;                /* 0 normal, 1 extended */
+  uint32_t start_rb;          /* first RB of the resource, from CRB 0 = grid PRB 0 */
+  uint32_t nof_rb;
+  uint32_t row;               /* csi_rs_mapping_table_row: 1..5 */
+  uint32_t nof_k_ref;         /* entries of freq_allocation_ref_idx: 1 for rows 1..5 */
+  uint32_t k_ref[6];          /* freq_allocation_ref_idx (k_0, ...) */
+  uint32_t symbol_l0;
+  uint32_t symbol_l1;         /* unused by rows 1..5 */
+  uint32_t cdm;               /* csi_rs_cdm_type: 0 no_CDM, 1 fd_CDM2, 2 cdm4_FD2_TD2, 3 cdm8_FD2_TD4 */
+  uint32_t freq_density;      /* csi_rs_freq_density_type: 0 dot5_even_RB, 1 dot5_odd_RB, 2 one, 3 three */
+  uint32_t scrambling_id;     /* 0..1023 */
+  float    amplitude;         /* linear; finite */
+  uint32_t nof_ports;         /* ports and layers of the precoding matrix: the row's ports */
+  float    precoding[4][4][2]; /* [port][layer] (re, im) */
+  uint32_t grid_index;        /* resource grid (slot) the signal is mapped into, < nof_grids */
+  uint32_t reserved;
+} srsgpu_csi_rs_config;
+
+typedef struct srsgpu_csi_rs_plan srsgpu_csi_rs_plan;
+
+/** Refuses, with the reference's reason as the message where it has one, what the pattern's assertions refuse (k_ref
+ *  count and range, density and CDM per row, l_0 outside the slot, the precoding's dimensions), rows above 5, row 5
+ *  with l_0 on the last symbol, RBs or ports outside the grid, an amplitude that is not finite, and two signals that
+ *  write the same REs (one launch gives them no order). */
+int srsgpu_csi_rs_plan_create(srsgpu_context*             ctx,
+                              const srsgpu_csi_rs_config* cfgs,
+                              uint32_t                    nof_signals,
+                              uint32_t                    grid_nof_prb,
+                              uint32_t                    grid_nof_ports,
+                              uint32_t                    nof_grids,
+                              srsgpu_csi_rs_plan**        plan);
+
+/** Writes every planned signal into d_grids (uint32 per RE: re | im << 16). One launch, asynchronous on `stream`,
+ *  allocation-free, hipGraph-capturable. */
+int srsgpu_csi_rs_plan_execute(const srsgpu_csi_rs_plan* plan, uint32_t* d_grids, void* stream);
+
+void srsgpu_csi_rs_plan_destroy(srsgpu_csi_rs_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PUCCH Formats 0 and 1 — replaces srsran::pucch_processor::process(grid, format0_configuration) and
  * process(grid, format1_batch_configuration) (lib/phy/upper/channel_processors/pucch/pucch_processor_impl.cpp:42 / :74)
  * with the detectors behind them (pucch_detector_format0.cpp:114, pucch_detector_format1.cpp:156) for every Format 0

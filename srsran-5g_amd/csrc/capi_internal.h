@@ -133,6 +133,8 @@ struct plan_deleter {
   void operator()(srsgpu_pdsch_modulator_plan* p) const { srsgpu_pdsch_modulator_plan_destroy(p); }
   void operator()(srsgpu_pdsch_dmrs_plan* p) const { srsgpu_pdsch_dmrs_plan_destroy(p); }
   void operator()(srsgpu_pdcch_plan* p) const { srsgpu_pdcch_plan_destroy(p); }
+  void operator()(srsgpu_ssb_plan* p) const { srsgpu_ssb_plan_destroy(p); }
+  void operator()(srsgpu_csi_rs_plan* p) const { srsgpu_csi_rs_plan_destroy(p); }
   void operator()(srsgpu_pucch_detector_plan* p) const { srsgpu_pucch_detector_plan_destroy(p); }
   void operator()(srsgpu_prach_detector_plan* p) const { srsgpu_prach_detector_plan_destroy(p); }
   void operator()(srsgpu_ofdm_plan* p) const { srsgpu_ofdm_plan_destroy(p); }

@@ -741,6 +741,31 @@ void launch_prach_detector(const prach_job*     d_jobs,
                            srsgpu_prach_result* d_results,
                            hipStream_t          stream);
 
+/// SS/PBCH blocks (ssb.hip): one block, one workgroup (ssb_host.h: the descriptors and the tables all blocks share).
+struct ssb_desc;
+struct ssb_tables;
+void launch_ssb(const ssb_desc*   d_descs,
+                uint32_t          nof_blocks,
+                const ssb_tables* d_tables,
+                const uint8_t*    d_payloads,
+                uint32_t*         d_grids,
+                const uint32_t*   d_x1,
+                const uint32_t*   d_x2_jump,
+                const uint32_t*   d_x2_lane,
+                hipStream_t       stream);
+
+/// NZP-CSI-RS (csi_rs.hip): one job per CDM group of a signal (csi_rs_host.h), cut into runs of 256 sequence elements;
+/// max_seq_len is the longest job's.
+struct csi_rs_job;
+void launch_csi_rs(const csi_rs_job* d_jobs,
+                   uint32_t          nof_jobs,
+                   uint32_t          max_seq_len,
+                   uint32_t*         d_grids,
+                   const uint32_t*   d_x1,
+                   const uint32_t*   d_x2_jump,
+                   const uint32_t*   d_x2_lane,
+                   hipStream_t       stream);
+
 void launch_pusch_demodulate_tp(const demod_desc*       d_desc,
                                 const demod_tp_job*      d_jobs,
                                 int                      nof_jobs,

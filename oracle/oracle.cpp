@@ -268,24 +268,72 @@ int orc_ldpc_encode(int bg, int Z, const uint8_t* msg, uint8_t* cb)
 // out: K*Z unpacked decoded bits. crc_poly < 0: no CRC early stop.
 // Returns the number of iterations when the CRC check succeeded, -1 otherwise (like std::nullopt).
 // Positions of a partial last node beyond n_llr are zero here (the reference leaves them stale when n_llr % Z != 0).
+//
+// orc_ldpc_decode_census is the same decoder with two test-side additions (tests/ldpc_regime_cases.py):
+//   counters (may be null): ORC_CENSUS_COUNT sums over the call that say which arithmetic regimes the input reached.
+//   defect: 0 decodes as the reference does; 1..ORC_DEFECT_COUNT - 1 each switch on ONE deliberate error, used only to
+//           show that a set of test inputs would notice a decoder with that error.
 // ---------------------------------------------------------------------------------------------------------------------
-int orc_ldpc_decode(int           mode,
-                    int           bg,
-                    int           Z,
-                    int           nof_crc_bits,
-                    int           nof_filler_bits,
-                    int           crc_poly,
-                    int           max_iter,
-                    float         scaling,
-                    const int8_t* llr,
-                    unsigned      n_llr,
-                    uint8_t*      out)
+enum orc_census {
+  CEN_LAYERS = 0,      // layers per iteration (decode :118-:128)
+  CEN_ITERATIONS,      // iterations run
+  CEN_ROWS,            // check-row evaluations (layers x Z x iterations)
+  CEN_EDGES,           // edge evaluations
+  CEN_V2C_INF,         // edges: |v2c| = LLR_INFTY
+  CEN_ROW_CAPPED,      // rows: min1 at the LLR_MAX cap (every edge >= LLR_MAX, argmin stays 0)
+  CEN_ROW_ONE_FINITE,  // rows: min1 < LLR_MAX = min2 (exactly one edge below the cap)
+  CEN_ROW_TIE,         // rows: min1 = min2 < LLR_MAX
+  CEN_V2C_ZERO,        // edges: v2c = 0
+  CEN_CANCEL,          // edges: c2v = -v2c, v2c != 0: the soft bit becomes 0
+  CEN_PROMOTE,         // edges: finite c2v + v2c beyond +/-LLR_MAX: the soft bit becomes +/-LLR_INFTY
+  CEN_CONFLICT,        // edges: infinite v2c met by a non-zero c2v of the other sign
+  CEN_V2C_CLAMP,       // edges: finite soft bit - c2v clamped at +/-LLR_MAX
+  CEN_MIN_TO_ZERO,     // rows: a positive min1 scaled to 0
+  CEN_INPUT_CLAMP,     // input LLRs changed by the +/-64 clamp of whole nodes
+  CEN_STOP_BLOCKED,    // iterations: CRC correct, early stop refused because a soft bit is 0
+  ORC_CENSUS_COUNT
+};
+
+enum orc_defect {
+  DEF_NONE = 0,
+  DEF_HARD_LT,         // hard decision soft < 0 instead of soft <= 0
+  DEF_STOP_ANY,        // early stop ignores the zero-soft-bit rule
+  DEF_MIN_127,         // minimum trackers start at LLR_INFTY instead of LLR_MAX
+  DEF_V2C_127,         // finite v2c clamped at +/-LLR_INFTY instead of +/-LLR_MAX
+  DEF_INF_OVERRIDE,    // a conflicting c2v is added to an infinite v2c; c2v = -v2c leaves the soft bit at v2c, not at 0
+  DEF_SKIP_LAST,       // the last layer is not run
+  DEF_INF_NOT_STICKY,  // v2c = clamp(soft - c2v) also for infinite soft bits
+  DEF_OTHER_SCALING,   // the other mode's scaling rule
+  ORC_DEFECT_COUNT
+};
+
+int orc_ldpc_decode_census(int           mode,
+                           int           bg,
+                           int           Z,
+                           int           nof_crc_bits,
+                           int           nof_filler_bits,
+                           int           crc_poly,
+                           int           max_iter,
+                           float         scaling,
+                           const int8_t* llr,
+                           unsigned      n_llr,
+                           uint8_t*      out,
+                           int           defect,
+                           uint64_t*     counters)
 {
   (void)nof_crc_bits;
+  uint64_t  unused[ORC_CENSUS_COUNT];
+  uint64_t* cen = counters != nullptr ? counters : unused;
+  std::memset(cen, 0, sizeof(unused));
   bg_view g;
-  if (!get_bg(bg, Z, g) || max_iter <= 0) {
+  if (!get_bg(bg, Z, g) || max_iter <= 0 || defect < 0 || defect >= ORC_DEFECT_COUNT) {
     return -2;
   }
+  if (defect == DEF_OTHER_SCALING) {
+    mode = mode == 0 ? 1 : 0;  // the modes differ in the scaling rule only
+  }
+  const int v2c_max  = defect == DEF_V2C_127 ? LLR_INF : LLR_MAX;
+  const int min_init = defect == DEF_MIN_127 ? LLR_INF : LLR_MAX;
   const int K       = g.K;
   const int msg_len = K * Z;
   if (static_cast<int>(n_llr) > g.N_short * Z || static_cast<int>(n_llr) < msg_len + 2 * Z) {
@@ -311,6 +359,7 @@ int orc_ldpc_decode(int           mode,
   for (int i = 0; i < full; ++i) {
     int v            = llr[i];
     soft[2 * Z + i]  = v > 64 ? 64 : (v < -64 ? -64 : v);
+    cen[CEN_INPUT_CLAMP] += (v > 64 || v < -64) ? 1 : 0;
   }
   for (int i = full; i < static_cast<int>(n_llr); ++i) {
     soft[2 * Z + i] = llr[i];
@@ -324,6 +373,8 @@ int orc_ldpc_decode(int           mode,
     cb_len = (cb_len / Z + 1) * Z;
   }
   const int nof_layers = cb_len / Z - K;
+  const int run_layers = defect == DEF_SKIP_LAST ? nof_layers - 1 : nof_layers;
+  cen[CEN_LAYERS]      = static_cast<uint64_t>(nof_layers);
 
   // Check-to-variable messages, stored per (edge, check row j) — the rotated domain of the reference.
   const int        nE = g.row_start[g.M];
@@ -356,28 +407,37 @@ int orc_ldpc_decode(int           mode,
     return -2;
   }
   const int nof_significant = msg_len - nof_filler_bits;
+  // get_hard_bits (:333): a soft bit of 0 reads as 1.
+  auto hard = [&](int sb) -> uint8_t { return (defect == DEF_HARD_LT ? sb < 0 : sb <= 0) ? 1 : 0; };
 
   for (int it = 0; it < max_iter; ++it) {
-    for (int m = 0; m < nof_layers; ++m) {
+    ++cen[CEN_ITERATIONS];
+    for (int m = 0; m < run_layers; ++m) {
       const int e0 = g.row_start[m], e1 = g.row_start[m + 1];
+      cen[CEN_ROWS] += static_cast<uint64_t>(Z);
+      cen[CEN_EDGES] += static_cast<uint64_t>(e1 - e0) * Z;
       for (int j = 0; j < Z; ++j) {
-        min1[j] = LLR_MAX;  // srsvec::fill(min, LLR_MAX) (:270)
-        min2[j] = LLR_MAX;
+        min1[j] = min_init;  // srsvec::fill(min, LLR_MAX) (:270)
+        min2[j] = min_init;
         idx[j]  = 0;
         sgn[j]  = 0;
       }
       // Variable-to-check messages (:195 + ldpc_decoder_avx2.cpp:69). c2v is always finite (|c2v| <= LLR_MAX because
-      // the minimum trackers start at LLR_MAX), so generic and SIMD saturation rules coincide here.
+      // the minimum trackers start at LLR_MAX), so generic and SIMD saturation rules coincide here: held against the
+      // reference on saturated and +/-127 inputs by tests/test_oracle_vs_reference.py (the regime grid).
       for (int e = e0; e < e1; ++e) {
         const int col = g.col[e], s = g.V[e] % Z, ei = e - e0;
         for (int j = 0; j < Z; ++j) {
           int sb = soft[col * Z + rot(j, s, Z)];
           int v;
-          if (sb >= LLR_INF || sb <= -LLR_INF) {
+          if ((sb >= LLR_INF || sb <= -LLR_INF) && defect != DEF_INF_NOT_STICKY) {
             v = sb;
+            ++cen[CEN_V2C_INF];
           } else {
             v = sb - c2v[static_cast<size_t>(e) * Z + j];
-            v = v > LLR_MAX ? LLR_MAX : (v < -LLR_MAX ? -LLR_MAX : v);
+            cen[CEN_V2C_CLAMP] += (v > LLR_MAX || v < -LLR_MAX) ? 1 : 0;
+            v = v > v2c_max ? v2c_max : (v < -v2c_max ? -v2c_max : v);
+            cen[CEN_V2C_ZERO] += v == 0 ? 1 : 0;
           }
           v2c[static_cast<size_t>(ei) * Z + j] = v;
           // analyze_var_to_check_msgs (ldpc_decoder_generic.cpp:46).
@@ -394,6 +454,12 @@ int orc_ldpc_decode(int           mode,
           sgn[j] ^= (v < 0) ? 1 : 0;
         }
       }
+      for (int j = 0; j < Z; ++j) {
+        cen[CEN_ROW_CAPPED] += min1[j] >= LLR_MAX ? 1 : 0;
+        cen[CEN_ROW_ONE_FINITE] += (min1[j] < LLR_MAX && min2[j] >= LLR_MAX) ? 1 : 0;
+        cen[CEN_ROW_TIE] += (min1[j] < LLR_MAX && min1[j] == min2[j]) ? 1 : 0;
+        cen[CEN_MIN_TO_ZERO] += (min1[j] > 0 && scale(min1[j]) == 0) ? 1 : 0;
+      }
       // Check-to-variable messages and soft-bit update (:255 + :240).
       for (int e = e0; e < e1; ++e) {
         const int col = g.col[e], s = g.V[e] % Z, ei = e - e0;
@@ -406,12 +472,16 @@ int orc_ldpc_decode(int           mode,
           // Promotion sum (log_likelihood_ratio.cpp:75, ldpc_decoder_avx2.cpp:205).
           int sb;
           if (v >= LLR_INF || v <= -LLR_INF) {
-            sb = v;
+            bool conflict = c != 0 && (c < 0) != (v < 0);
+            cen[CEN_CONFLICT] += conflict ? 1 : 0;
+            sb = (conflict && defect == DEF_INF_OVERRIDE) ? v + c : v;
           } else if (c == -v) {
-            sb = 0;
+            cen[CEN_CANCEL] += v != 0 ? 1 : 0;
+            sb = defect == DEF_INF_OVERRIDE ? v : 0;
           } else {
             int t = c + v;
             sb    = t > LLR_MAX ? LLR_INF : (t < -LLR_MAX ? -LLR_INF : t);
+            cen[CEN_PROMOTE] += (t > LLR_MAX || t < -LLR_MAX) ? 1 : 0;
           }
           soft[col * Z + rot(j, s, Z)] = sb;
         }
@@ -420,20 +490,43 @@ int orc_ldpc_decode(int           mode,
     if (crc_poly >= 0) {
       bool ok = true;
       for (int i = 0; i < msg_len; ++i) {
-        out[i] = soft[i] <= 0 ? 1 : 0;
+        out[i] = hard(soft[i]);
         ok &= soft[i] != 0;
       }
-      if (ok && orc_crc_bits(crc_poly, out, nof_significant) == 0) {
+      const bool crc_ok = orc_crc_bits(crc_poly, out, nof_significant) == 0;
+      cen[CEN_STOP_BLOCKED] += (crc_ok && !ok) ? 1 : 0;
+      if ((ok || defect == DEF_STOP_ANY) && crc_ok) {
         return it + 1;
       }
     }
   }
   if (crc_poly < 0) {
     for (int i = 0; i < msg_len; ++i) {
-      out[i] = soft[i] <= 0 ? 1 : 0;
+      out[i] = hard(soft[i]);
     }
   }
   return -1;
+}
+
+int orc_ldpc_decode(int           mode,
+                    int           bg,
+                    int           Z,
+                    int           nof_crc_bits,
+                    int           nof_filler_bits,
+                    int           crc_poly,
+                    int           max_iter,
+                    float         scaling,
+                    const int8_t* llr,
+                    unsigned      n_llr,
+                    uint8_t*      out)
+{
+  return orc_ldpc_decode_census(
+      mode, bg, Z, nof_crc_bits, nof_filler_bits, crc_poly, max_iter, scaling, llr, n_llr, out, DEF_NONE, nullptr);
+}
+
+int orc_ldpc_census_count()
+{
+  return ORC_CENSUS_COUNT;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -46,6 +46,30 @@ def decoder_cases():
         oo += ob
 
 
+REGIME_FAMILIES = ["baseline", "low", "unit", "saturated", "two_valued", "pm127", "noisy"]
+
+
+def decoder_regime_cases():
+    """Yields dict(bg, Z, li (length index), layers, family, kind, crc_poly (-1 none), nof_crc_bits, filler, max_iter, llr,
+    iters {impl: -1 = nullopt}, bits {impl: ...}) with impl 0 generic / 1 avx2: the reference's outputs on the regime
+    grid of tests/ldpc_regime_cases.py at its GOLDEN_Z lifting sizes (tools/gen_golden.py gen_ldpc_decoder_regimes)."""
+    d = _load("ldpc_decoder_regimes.npz")
+    cfg = d["cfg"]
+    ob = [(BG_K[bg] * Z + 7) // 8 for bg, Z in cfg[:, :2]]
+    total = sum(ob)
+    lo = oo = 0
+    for i, (bg, Z, li, fam, kind, poly, nbits, filler, max_iter, n_llr) in enumerate(cfg):
+        K = BG_K[bg] * Z
+        layers = (4, 8, 9, 16, 17, BG_N_SHORT[bg] + 2 - BG_K[bg])[li]
+        yield dict(bg=int(bg), Z=int(Z), li=int(li), layers=layers, family=REGIME_FAMILIES[fam], kind=("family", "two_iter")[kind],
+                   crc_poly=int(poly), nof_crc_bits=int(nbits), filler=int(filler), max_iter=int(max_iter), sf=0.8,
+                   llr=d["llr"][lo:lo + n_llr], iters={impl: int(d["iters"][impl, i]) for impl in (0, 1)},
+                   bits={impl: np.unpackbits(d["out"][impl * total + oo:impl * total + oo + ob[i]])[:K]
+                         for impl in (0, 1)})
+        lo += n_llr
+        oo += ob[i]
+
+
 def rate_matching_cases():
     """Yields dict(bg, Z, rv, qm, Nref, filler, E, msg, rm_out, dm_llr, dm_init, dm_out[(new_data, impl)])."""
     d = _load("rate_matching.npz")

@@ -139,6 +139,15 @@ def pdsch_mod_nof_re(cfg):
     return n
 
 
+# Counters of Oracle.ldpc_decode_census, in the order of oracle.cpp's orc_census.
+CENSUS = ["layers", "iterations", "rows", "edges", "v2c_inf", "row_capped", "row_one_finite", "row_tie", "v2c_zero",
+          "cancel", "promote", "conflict", "v2c_clamp", "min_to_zero", "input_clamp", "stop_blocked"]
+CEN = {name: i for i, name in enumerate(CENSUS)}
+# Deliberate decoder errors of Oracle.ldpc_decode_census (oracle.cpp orc_defect); 0 is the faithful decoder.
+DEFECTS = ["none", "hard_lt", "stop_any", "min_127", "v2c_127", "inf_override", "skip_last", "inf_not_sticky",
+           "other_scaling"]
+
+
 class Oracle(_Lib):
     def __init__(self, path=ORACLE_SO):
         super().__init__(path, "orc_")
@@ -149,6 +158,21 @@ class Oracle(_Lib):
         r = self.lib.orc_ldpc_encode(bg, Z, _ptr(msg), _ptr(cb))
         assert r == 0, r
         return cb
+
+    def ldpc_decode_census(self, mode, bg, Z, llr, nof_crc_bits=16, nof_filler=0, crc_poly=-1, max_iter=6, scaling=0.8,
+                           defect=0):
+        """orc_ldpc_decode_census: ldpc_decode plus the regime counters of the call (uint64, indexed by CENSUS) and,
+        with defect in 1..len(DEFECTS) - 1, one deliberate decoder error (DEFECTS). Oracle only."""
+        f = self.lib.orc_ldpc_decode_census
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_int] * 7 + [ctypes.c_float, _P, ctypes.c_uint, _P, ctypes.c_int, _P]
+        assert self.lib.orc_ldpc_census_count() == len(CENSUS)
+        llr = np.ascontiguousarray(llr, dtype=np.int8)
+        out = np.zeros(BG_K[bg] * Z, np.uint8)
+        counters = np.zeros(len(CENSUS), np.uint64)
+        r = f(mode, bg, Z, nof_crc_bits, nof_filler, crc_poly, max_iter, scaling, _ptr(llr), llr.size, _ptr(out),
+              int(defect), _ptr(counters))
+        return r, out, counters
 
     def rate_match(self, bg, Z, rv, qm, Nref, nof_filler, cb, E):
         cb = np.ascontiguousarray(cb, dtype=np.uint8)

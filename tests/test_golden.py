@@ -38,6 +38,28 @@ def test_decoder_golden(orc):
     assert nsucc > 20 and nfail > 20
 
 
+def test_decoder_regimes_golden(orc):
+    """The oracle against the reference's recorded outputs on the regime grid's fixture subset (nine lifting sizes, both
+    base graphs, every layer class and boundary, every LLR family, both arithmetics); the fixture's inputs are the
+    case module's own, so the fixture and the GPU tests speak of the same codeblocks."""
+    import ldpc_regime_cases as R
+    cases = list(G.decoder_regime_cases())
+    assert len(cases) == 2 * 2 * len(R.GOLDEN_Z) * 6
+    assert {c["family"] for c in cases} == set(R.FAMILIES) | {"noisy"}
+    assert {c["Z"] for c in cases} == set(R.GOLDEN_Z) and {c["li"] for c in cases} == set(range(6))
+    for c, mine in zip(cases, R.build_grid(orc, sizes=R.GOLDEN_Z)):
+        assert np.array_equal(c["llr"], mine["llr"]) and c["crc_poly"] == mine["crc_poly"], (c["bg"], c["Z"], c["li"])
+    for impl in (0, 1):
+        for c in cases:
+            r, bits = orc.ldpc_decode(impl, c["bg"], c["Z"], c["llr"], nof_crc_bits=c["nof_crc_bits"],
+                                      nof_filler=c["filler"], crc_poly=c["crc_poly"], max_iter=c["max_iter"],
+                                      scaling=0.8)
+            assert r == c["iters"][impl], (impl, c["bg"], c["Z"], c["li"], c["family"])
+            assert np.array_equal(bits, c["bits"][impl]), (impl, c["bg"], c["Z"], c["li"], c["family"])
+        ok = [c["iters"][impl] >= 0 for c in cases if c["crc_poly"] >= 0]
+        assert 0.2 < sum(ok) / len(ok) < 0.8
+
+
 def test_rate_matching_golden(orc):
     for c in G.rate_matching_cases():
         cb = orc.ldpc_encode(c["bg"], c["Z"], c["msg"])

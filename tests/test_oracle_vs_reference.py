@@ -112,6 +112,27 @@ def test_decoder_scaling_factors(orc, ref):
             assert r1 == r2 and np.array_equal(o1, o2), sf
 
 
+@pytest.mark.parametrize("which", ["grid", "sweep"])
+def test_decoder_regime_grid_matches_reference(orc, ref, which):
+    """The regime grid and the scaling sweep (tests/ldpc_regime_cases.py): every lifting size in every layer class and on
+    the class boundaries, LLRs of amplitude 1 and 2, saturated, two-valued and +/-127 with wrong signs. These are the
+    inputs on which the oracle's reasoning about saturation ("c2v is always finite") is put to the reference: generic,
+    AVX2 and, where the CPU has it, AVX-512. Bits and iteration count equal."""
+    import ldpc_regime_cases as R
+    cases, res = R.grid_with_results(orc) if which == "grid" else R.sweep_with_results(orc)
+    impls = [(0, Reference.GENERIC), (1, Reference.AVX2)]
+    if ref.has_avx512():
+        impls.append((1, Reference.AVX512))
+    for mode, impl in impls:
+        for i, (c, (r_orc, o_orc)) in enumerate(zip(cases, res[mode][0])):
+            r_ref, o_ref = ref.ldpc_decode(impl, c["bg"], c["Z"], c["llr"], nof_crc_bits=c["nof_crc_bits"],
+                                           nof_filler=c["filler"], crc_poly=c["crc_poly"], max_iter=c["max_iter"],
+                                           scaling=c["sf"])
+            key = (impl, i, c["bg"], c["Z"], c["li"], c["family"], c["kind"], c["sf"])
+            assert (None if r_ref < 0 else r_ref) == r_orc, key
+            assert np.array_equal(o_ref, o_orc), key
+
+
 def _rm_cases():
     rng = np.random.default_rng(3)
     cases = []

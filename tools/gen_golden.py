@@ -97,6 +97,41 @@ def gen_decoder(ref, rng):
                         llr=np.concatenate(llrs), iters=np.array(iters, np.int32), out=np.concatenate(outs))
 
 
+def save_npz_fixed(path, **arrays):
+    """np.savez_compressed with fixed member timestamps: the same arrays give the same bytes on every run."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(a), allow_pickle=False)
+
+
+def gen_ldpc_decoder_regimes(ref, rng):
+    """The regime grid of tests/ldpc_regime_cases.py at the lifting sizes GOLDEN_Z (both base graphs, every length, so
+    every layer class and boundary, every LLR family, the two-iteration codeblocks), decoded by the reference's
+    generic and AVX2 decoders. Rows: (bg, Z, length index, family, kind, crc_poly or -1, nof_crc_bits, filler,
+    max_iter, n_llr); iters and out hold the generic results, then the AVX2 ones. The cases carry their own seeds."""
+    import ldpc_regime_cases as R
+    from oracle_lib import Oracle
+    cases = R.build_grid(Oracle(), sizes=R.GOLDEN_Z)
+    kinds = ["family", "two_iter"]
+    cfg = [(c["bg"], c["Z"], c["li"], (R.FAMILIES + ["noisy"]).index(c["family"]), kinds.index(c["kind"]),
+            c["crc_poly"], c["nof_crc_bits"], c["filler"], c["max_iter"], c["llr"].size) for c in cases]
+    iters, outs = [], []
+    for impl in (Reference.GENERIC, Reference.AVX2):
+        for c in cases:
+            r, o = ref.ldpc_decode(impl, c["bg"], c["Z"], c["llr"], nof_crc_bits=c["nof_crc_bits"],
+                                   nof_filler=c["filler"], crc_poly=c["crc_poly"], max_iter=c["max_iter"], scaling=0.8)
+            iters.append(r)
+            outs.append(np.packbits(o))
+    save_npz_fixed(os.path.join(OUT, "ldpc_decoder_regimes.npz"), cfg=np.array(cfg, np.int32),
+                   llr=np.concatenate([c["llr"] for c in cases]), iters=np.array(iters, np.int32).reshape(2, -1),
+                   out=np.concatenate(outs))
+
+
 def gen_rate_matching(ref, rng):
     """Per case: message, rate-matched output, dematcher input/initial buffer and the four dematcher outputs
     (new_data 1/0 x generic/SIMD combining)."""
@@ -435,7 +470,7 @@ def main():
         for name in sys.argv[1:]:
             seed = {"ofdm": 16, "pusch_demod": 17, "pusch_chest": 18, "pdsch_dmrs": 19, "pusch_chest_cfo": 20,
                     "pdsch_mod_general": 21, "pdsch_dmrs_mask": 22, "pusch_demod_general": 23, "ulsch_demux": 24, "pusch_chest_low_papr": 25,
-                    "pusch_chest_273": 26}[name]
+                    "pusch_chest_273": 26, "ldpc_decoder_regimes": 27}[name]
             globals()["gen_" + name](ref, np.random.default_rng(seed))
         return
     gen_crc(ref, np.random.default_rng(10))
@@ -455,6 +490,7 @@ def main():
     gen_ulsch_demux(ref, np.random.default_rng(24))
     gen_pusch_chest_low_papr(ref, np.random.default_rng(25))
     gen_pusch_chest_273(ref, np.random.default_rng(26))
+    gen_ldpc_decoder_regimes(ref, np.random.default_rng(27))
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

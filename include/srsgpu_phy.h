@@ -728,6 +728,84 @@ void srsgpu_prach_detector_plan_destroy(srsgpu_prach_detector_plan* plan);
 int srsgpu_prach_max_delay_samples(uint32_t format, uint32_t ra_scs, uint32_t n_cs, uint32_t* max_delay_samples);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * SRS estimator — replaces srsran::srs_estimator::estimate(const resource_grid_reader&, const
+ * srs_estimator_configuration&) (include/srsran/phy/upper/signal_processors/srs/srs_estimator.h, the generic estimator
+ * of lib/phy/upper/signal_processors/srs/srs_estimator_generic_impl.cpp:79 with get_srs_information of
+ * lib/ran/srs/srs_information.cpp:38, the DFT time alignment estimator of
+ * lib/phy/support/time_alignment_estimator/time_alignment_estimator_dft_impl.cpp:174 / :245 and the low-PAPR sequences
+ * of lib/phy/upper/sequence_generators/low_papr_sequence_generator_impl.cpp:243) for every SRS resource of a batch of
+ * slots in one launch, from bf16 grids of the uplink plans' layout to the wideband channel matrix, the EPRE, the noise
+ * variance and the time alignment.
+ *
+ * A resource carries physical values. The row of TS 38.211 Table 6.4.1.4.3-1 that C_SRS selects arrives as data: the
+ * four (m_srs[b], N[b]) pairs, which a binding fills from srs_configuration_get(c_srs, b), b = 0..3. Subcarriers are
+ * grid subcarriers. All powers are linear; the caller takes 10 log10. The reference reports time_alignment.min as the
+ * smallest positive double (srs_estimator_generic_impl.cpp:115 / :203); the plan reports ta_max only and the lower
+ * bound is -ta_max. Frequency, group and sequence hopping are not supported (the reference refuses them).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint16_t m_srs[4];          /* m_SRS,b of the C_SRS row, b = 0..3: multiples of 4, m_srs[b] N[b] = m_srs[b - 1] */
+  uint8_t  N[4];              /* N_b of the row; N[0] = 1 */
+  uint8_t  numerology;        /* 0..4: the subcarrier spacing, 15 kHz << numerology */
+  uint8_t  nof_antenna_ports; /* 1, 2 or 4 */
+  uint8_t  nof_symbols;       /* 1, 2 or 4 */
+  uint8_t  start_symbol;      /* start_symbol + nof_symbols <= 14 */
+  uint8_t  comb_size;         /* K_TC: 2 or 4 */
+  uint8_t  comb_offset;       /* < comb_size */
+  uint8_t  cyclic_shift;      /* < 8 (comb 2) or < 12 (comb 4) */
+  uint8_t  bandwidth_index;   /* B_SRS, 0..3 */
+  uint8_t  freq_hopping;      /* b_hop, 0..3; below bandwidth_index is frequency hopping, which is refused */
+  uint8_t  hopping;           /* group_or_sequence_hopping_enum: 0 neither; anything else is refused */
+  uint8_t  nof_rx_ports;      /* 1..4 */
+  uint8_t  reserved;
+  uint8_t  rx_ports[4];       /* grid ports, in the order of srs_estimator_configuration::ports */
+  uint16_t sequence_id;       /* n_ID^SRS, 0..1023 */
+  uint16_t freq_shift;        /* n_shift, 0..268 */
+  uint16_t freq_position;     /* n_RRC, 0..67 */
+  uint16_t reserved2;
+  uint32_t grid_index;        /* < nof_grids */
+  uint32_t result_index;      /* the resource's srsgpu_srs_result; a permutation of 0..nof_resources-1 over the plan */
+} srsgpu_srs_config;
+
+/** One per resource, 192 bytes, every byte written by every execute. */
+typedef struct {
+  float    channel[4][4][2];  /* [rx port index][tx port] (re, im): srs_channel_matrix; unused entries zero */
+  double   time_alignment;    /* seconds: the mean over the tx ports */
+  double   resolution;        /* 1 / fs, fs = IDFT size x subcarrier spacing x comb_size */
+  double   ta_max;            /* max_ta_samples / fs; the measurement lies in [-ta_max, ta_max] */
+  float    epre;              /* linear */
+  float    noise_var;         /* linear */
+  int32_t  ta_idx[4];         /* per tx port: the peak's tap before the fractional refinement (negative: advanced) */
+  uint32_t reserved[4];       /* written as zero */
+} srsgpu_srs_result;
+
+typedef struct srsgpu_srs_estimator_plan srsgpu_srs_estimator_plan;
+
+/** Refuses what srs_validator_generic_impl::is_valid and the estimator's assertions refuse (an invalid resource,
+ *  frequency hopping, group or sequence hopping, no rx port, a resource past the grid, start_symbol + nof_symbols > 14)
+ *  and in addition: port, symbol or comb counts outside their sets, an rx port outside the grid or listed twice, a
+ *  table row that is not self-consistent, a grid outside the grids, and a result_index outside the resources or used
+ *  twice. The bandwidth check walks the antenna ports (the reference's validator walks the rx port count,
+ *  srs_validator_generic_impl.cpp:52-53). Blocking. */
+int srsgpu_srs_estimator_plan_create(srsgpu_context*             ctx,
+                                     const srsgpu_srs_config*    resources,
+                                     uint32_t                    nof_resources,
+                                     uint32_t                    grid_nof_prb,
+                                     uint32_t                    grid_nof_ports,
+                                     uint32_t                    nof_grids,
+                                     srsgpu_srs_estimator_plan** plan);
+
+/** Estimates every planned resource: reads d_grids (uint32 per RE: re | im << 16, bf16; nof_grids x ports x 14 x
+ *  12 PRBs) and writes every byte of the nof_resources results. One launch, one workgroup per resource, asynchronous
+ *  on `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_srs_estimator_plan_execute(const srsgpu_srs_estimator_plan* plan,
+                                      const uint32_t*                  d_grids,
+                                      srsgpu_srs_result*               d_results,
+                                      void*                            stream);
+
+void srsgpu_srs_estimator_plan_destroy(srsgpu_srs_estimator_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

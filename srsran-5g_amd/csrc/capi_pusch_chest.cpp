@@ -3,7 +3,7 @@
 // (port_channel_estimator_helpers.cpp filter_type, taps generated from the raised-cosine formula) and one job per
 // (transmission, rx port, CDM group).
 #include "capi_internal.h"
-#include "low_papr_tables.h"
+#include "low_papr_host.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -57,54 +57,6 @@ unsigned ta_dft_size(unsigned nof_re)
     size <<= 1;
   }
   return std::max(128u, size);
-}
-
-/// TS 38.211 section 5.2.2 low-PAPR base sequence of group u (v = 0, alpha = 0) and length m, as
-/// low_papr_sequence_generator_impl.cpp builds it: the phase tables for m = 6..24, the length-30 formula, and
-/// Zadoff-Chu of the largest prime N_ZC < m for m >= 36 with q = (int)(q_hat + 0.5), q_hat = (float) N_ZC (u + 1) / 31.
-/// Returns false for a length the specification does not define.
-bool low_papr_sequence(unsigned u, unsigned m, std::vector<float2>& out)
-{
-  std::vector<int> arg(m);
-  unsigned         nzc = 4;
-  const int8_t*    phi = m == 6 ? kLowPaprPhi6[u] : m == 12 ? kLowPaprPhi12[u] : m == 18 ? kLowPaprPhi18[u]
-                                                                  : m == 24 ? kLowPaprPhi24[u] : nullptr;
-  if (phi != nullptr) {
-    for (unsigned n = 0; n < m; ++n) {
-      arg[n] = phi[n];  // units of pi / 4 = pi / N_ZC with N_ZC = 4
-    }
-  } else if (m == 30) {
-    nzc = 31;
-    for (unsigned n = 0; n < m; ++n) {
-      arg[n] = -static_cast<int>(((u + 1ull) * (n + 1ull) * (n + 2ull)) % 62u);
-    }
-  } else if (m >= 36) {
-    nzc = m - 1;
-    auto prime = [](unsigned x) {
-      for (unsigned d = 2; d * d <= x; ++d) {
-        if (x % d == 0) {
-          return false;
-        }
-      }
-      return x > 1;
-    };
-    while (!prime(nzc)) {
-      --nzc;
-    }
-    const float   q_hat = static_cast<float>(nzc) * static_cast<float>(u + 1) / 31.f;
-    const int64_t q     = static_cast<int64_t>(static_cast<float>(static_cast<double>(q_hat) + 0.5));
-    for (unsigned n = 0; n < m; ++n) {
-      const int64_t mm = n % nzc;
-      arg[n]           = -static_cast<int>((q * mm * (mm + 1)) % (2 * nzc));
-    }
-  } else {
-    return false;
-  }
-  for (unsigned n = 0; n < m; ++n) {
-    const double a = 3.14159265358979323846 * static_cast<double>(arg[n]) / static_cast<double>(nzc);
-    out.push_back(make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a))));
-  }
-  return true;
 }
 
 } // namespace

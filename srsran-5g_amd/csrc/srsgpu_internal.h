@@ -741,6 +741,17 @@ void launch_prach_detector(const prach_job*     d_jobs,
                            srsgpu_prach_result* d_results,
                            hipStream_t          stream);
 
+/// SRS estimator (srs_estimator.hip): one workgroup per job (srs_host.h: one resource), the antenna ports' sequences
+/// and the 1024-entry phase table as (re, im) floats, and one srsgpu_srs_result per resource.
+struct srs_job;
+void launch_srs_estimator(const srs_job*     d_jobs,
+                          uint32_t           nof_jobs,
+                          const float*       d_seqs,
+                          const float*       d_cexp,
+                          const uint32_t*    d_grids,
+                          srsgpu_srs_result* d_results,
+                          hipStream_t        stream);
+
 /// SS/PBCH blocks (ssb.hip): one block, one workgroup (ssb_host.h: the descriptors and the tables all blocks share).
 struct ssb_desc;
 struct ssb_tables;

@@ -1195,6 +1195,11 @@ int srsgpu_pdsch_encoder_plan_create(srsgpu_context*               ctx,
     plan->count[b]    = static_cast<int>(encs[b].size());
     plan->count_pk[b] = static_cast<int>(encs_pk[b].size());
     plan->threads[b]  = ((maxz[b] + 63) / 64) * 64;
+    // Packed codeblocks that carry their TB's CRC (the kernel's own test) go first, in their original order: their
+    // workgroups also run the TB CRC, so they start in the first round and the shorter ones fill in behind them. A
+    // descriptor holds its own TB and output offsets; nothing else depends on the order.
+    std::stable_partition(encs_pk[b].begin(), encs_pk[b].end(),
+                          [](const enc_desc& d) { return d.tb_bit_offset + d.nof_data > d.tb_bits; });
     encs[b].insert(encs[b].end(), encs_pk[b].begin(), encs_pk[b].end());
     ok = plan->d_enc[b].upload(encs[b]);
   }

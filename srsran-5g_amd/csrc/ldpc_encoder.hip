@@ -520,14 +520,23 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
 {
   using G = ebg<BG>;
   constexpr int WMAX = 384 / 32;
-  __shared__ uint32_t cw[G::NF * WMAX + 1];        // packed codeblock, node c at c * W
-  __shared__ uint32_t lam[4 * WMAX];               // core row sums
+  // LDS: 16 workgroups per CU need <= 10 240 B. The codeblock words, the core row sums and the edge table are first
+  // written after both CRCs, and the TB CRC's slice-by-4 tables (the carrier only) are last read before that: they
+  // share one region.
+  constexpr int CW_WORDS  = G::NF * WMAX + 1;
+  constexpr int LAM_WORDS = 4 * WMAX;
+  constexpr int LATE_WORDS = CW_WORDS + LAM_WORDS + G::NE;
+  constexpr int UNI_WORDS = LATE_WORDS > static_cast<int>(CRC_SLICE_WORDS) ? LATE_WORDS
+                                                                            : static_cast<int>(CRC_SLICE_WORDS);
+  __shared__ uint32_t uni[UNI_WORDS];
+  uint32_t* const       cw   = uni;                         // packed codeblock, node c at c * W
+  uint32_t* const       lam  = uni + CW_WORDS;              // core row sums
+  uint32_t* const       edge = uni + CW_WORDS + LAM_WORDS;  // column << 16 | lifted shift of every base-graph edge
+  const uint32_t* const t4t  = uni;  // TB CRC (24A or 16) slice-by-4 tables, until the TB CRC is known
   __shared__ __attribute__((aligned(4))) uint8_t msg[G::K * 384 / 8];  // message bytes, MSB first
-  __shared__ uint32_t edge[G::NE];                 // column << 16 | lifted shift of every base-graph edge
   __shared__ uint16_t row_start[G::M + 1];
   __shared__ uint32_t red[PK_THREADS / WAVE];
   __shared__ uint32_t t4b[CRC_SLICE_WORDS];        // CB CRC24B slice-by-4 tables
-  __shared__ uint32_t t4t[CRC_SLICE_WORDS];        // TB CRC (24A or 16) slice-by-4 tables (the carrier only)
 
   ENC_STAMP(0);
   ENC_PROF(9, __builtin_amdgcn_s_memrealtime());
@@ -600,7 +609,7 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
       }
     }
   }
-  // Slice-by-4 CRC tables from the context (L2-resident, 8 words per lane; the barriers below publish them).
+  // Slice-by-4 CRC tables from the context (L2-resident, 8 words per lane; the barrier below publishes them).
   constexpr int TW = CRC_SLICE_WORDS / PK_THREADS;
   if (has_cbc) {
     const uint32_t* src = crc_slice + CRC_SLICE_24B * CRC_SLICE_WORDS;
@@ -623,21 +632,28 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
     }
 #pragma unroll
     for (int q = 0; q < TW; ++q) {
-      t4t[tid + q * PK_THREADS] = t[q];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < NEL; ++r) {
-    if (tid + r * PK_THREADS < G::NE) {
-      edge[tid + r * PK_THREADS] = ev[r];
+      uni[tid + q * PK_THREADS] = t[q];
     }
   }
   for (int m = tid; m <= G::M; m += PK_THREADS) {
     row_start[m] = static_cast<uint16_t>(G::rs(m));
   }
-  // ---- Message bytes (ldpc_segmenter_tx_impl.cpp:144): TB(+TB CRC) bytes, zero padding / CRC slot / fillers. ----
+  // ---- Message bytes (ldpc_segmenter_tx_impl.cpp:144): TB(+TB CRC) bytes, zero padding / CRC slot / fillers. A
+  // carrier's TB CRC bytes are zero here (tb_crc is) and written once the CRC is known. ----
+#pragma unroll
+  for (int r = 0; r < MB; ++r) {
+    const int q = tid + r * PK_THREADS;
+    if (q < nkb) {
+      const uint32_t p = d.tb_bit_offset + 8u * static_cast<uint32_t>(q);
+      uint32_t       b = byte[r];
+      if (q < nd8 && p >= d.tb_bits) {
+        b = (tb_crc >> (d.tb_crc_len - 8u - (p - d.tb_bits))) & 0xffu;
+      }
+      msg[q] = static_cast<uint8_t>(b);
+    }
+  }
+  __syncthreads();  // msg, t4b and t4t complete
   if (tfast) {
-    __syncthreads();  // t4t complete
     const int order  = static_cast<int>(tcd.order);
     const int nb     = static_cast<int>(tcd.nbytes);
     uint32_t  rem[2] = {0u, 0u};
@@ -663,33 +679,29 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
     if ((tid % WAVE) == 0) {
       red[tid / WAVE] = acc;
     }
-    __syncthreads();
+    __syncthreads();  // also the last read of t4t
 #pragma unroll
     for (int w = 0; w < PK_THREADS / WAVE; ++w) {
       tb_crc ^= red[w];
     }
   } else if (carrier) {
-    __syncthreads();  // t4t complete
     const uint8_t* tbp = tbs + tcd.byte_offset;
     tb_crc = block_crc_slice4<16>([tbp](int i) { return tbp[i]; }, static_cast<int>(tcd.nbytes),
                                   crc_tables + tcd.table, static_cast<int>(tcd.order), tcd.poly, t4t, red);
   }
   ENC_STAMP(1);
-#pragma unroll
-  for (int r = 0; r < MB; ++r) {
-    const int q = tid + r * PK_THREADS;
-    if (q < nkb) {
-      const uint32_t p = d.tb_bit_offset + 8u * static_cast<uint32_t>(q);
-      uint32_t       b = byte[r];
-      if (q < nd8 && p >= d.tb_bits) {
-        b = (tb_crc >> (d.tb_crc_len - 8u - (p - d.tb_bits))) & 0xffu;
-      }
-      msg[q] = static_cast<uint8_t>(b);
+  if (carrier) {  // the TB CRC's bytes: message bytes [qc, nd8), at most three
+    const int qc = static_cast<int>(d.tb_bits - min(d.tb_bit_offset, d.tb_bits)) / 8;
+    if (tid < nd8 - qc) {
+      const uint32_t p = d.tb_bit_offset + 8u * static_cast<uint32_t>(qc + tid);
+      msg[qc + tid]    = static_cast<uint8_t>((tb_crc >> (d.tb_crc_len - 8u - (p - d.tb_bits))) & 0xffu);
     }
   }
   ENC_STAMP(2);
   if (has_cbc) {
-    __syncthreads();  // msg and lut_b complete
+    if (carrier) {
+      __syncthreads();  // the TB CRC's bytes in msg
+    }
     const uint32_t crc = block_crc_slice4<CB_CS>([](int q) { return msg[q]; }, cb_bytes, crc_tables + d.crc_table, 24,
                                                  0x1800063u, t4b, red, pre_m, m0);
     if (tid < 3) {
@@ -698,13 +710,20 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
   }
   __syncthreads();
   ENC_STAMP(3);
-  // ---- Message words: node c word k = message bits 32 (c W + k) .. + 31. ----
+  // ---- Message words: node c word k = message bits 32 (c W + k) .. + 31; the edge table (its region held the TB
+  // CRC's tables until here). ----
   const uint32_t* msg32 = reinterpret_cast<const uint32_t*>(msg);
   for (int q = tid; q < K * W; q += PK_THREADS) {
     cw[q] = bytes_bitrev(msg32[q]);
   }
   if (tid < 4 * WMAX) {
     lam[tid] = 0u;
+  }
+#pragma unroll
+  for (int r = 0; r < NEL; ++r) {
+    if (tid + r * PK_THREADS < G::NE) {
+      edge[tid + r * PK_THREADS] = ev[r];
+    }
   }
   __syncthreads();
   ENC_STAMP(4);

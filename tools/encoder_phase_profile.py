@@ -6,7 +6,8 @@ Build the instrumented library first (next to, not over, the product library):
 then on the GPU:
     SRSGPU_LIB=srsran-5g_amd/lib_prof/libsrsgpu_phy.so python tools/encoder_phase_profile.py
 
-Each codeblock's workgroup stamps s_memtime at: start (0), after the inline TB CRC (1), after the message bytes (2),
+Each codeblock's workgroup stamps s_memtime at: start (0), after the message bytes and the inline TB CRC (1), after the
+TB CRC's bytes (2),
 after the CB CRC (3), after the message words (4), after the core rows (5), after p0..p3 (6), after the extension
 rows (7), after rate matching (8); s_memrealtime (100 MHz) at start / end (9 / 10).
 """
@@ -67,7 +68,7 @@ def main():
     for k, name in enumerate(PHASES):
         res[name + "_cycles"] = float((p[:, k + 1] - p[:, k]).mean())
     res["total_cycles_per_cb"] = float((p[:, 8] - p[:, 0]).mean())
-    last_cb = (p[:, 1] - p[:, 0]) > 2 * np.median(p[:, 1] - p[:, 0]) + 100
+    last_cb = np.flatnonzero(ok) < len(segs) * S  # the plan uploads the TB-CRC carriers, one per TB, first
     res["tb_crc_cycles_on_tb_crc_carriers"] = float((p[last_cb, 1] - p[last_cb, 0]).mean()) if last_cb.any() else 0.0
     res["tb_crc_carriers"] = int(last_cb.sum())
     wall = (p[:, 10] - p[:, 9]) / 100.0

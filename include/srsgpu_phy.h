@@ -806,6 +806,77 @@ int srsgpu_srs_estimator_plan_execute(const srsgpu_srs_estimator_plan* plan,
 void srsgpu_srs_estimator_plan_destroy(srsgpu_srs_estimator_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH Format 2 front end — the part of srsran::pucch_processor::process(const resource_grid_reader&, const
+ * format2_configuration&) (lib/phy/upper/channel_processors/pucch/pucch_processor_impl.cpp:145) in front of the UCI
+ * decoder: dmrs_pucch_estimator_format2::estimate (lib/phy/upper/signal_processors/pucch/
+ * dmrs_pucch_estimator_format2.cpp:87, over port_channel_estimator_average_impl with filter smoothing, the average
+ * time strategy and no CFO compensation) and pucch_demodulator_format2::demodulate
+ * (lib/phy/upper/channel_processors/pucch/pucch_demodulator_format2.cpp:92: ZF 1 x N, QPSK, descrambling), for every
+ * Format 2 PDU of a batch of slots in one launch, from bf16 grids of the uplink plans' layout to descrambled int8 LLRs
+ * and the per-port channel state. The LLRs lie where srsgpu_uci_decoder_plan (3..11 bits, Qm 2) and
+ * srsgpu_uci_polar_decoder_plan (12 bits and more) read them in place: E = 16 nof_prb nof_symbols at llr_offset.
+ *
+ * PRBs are grid PRBs (the BWP start already added). Group hopping is NEITHER in the reference's processor and no
+ * parameter here. As in the reference, the data REs of receive port i are read from grid port i and its pilots from
+ * grid port ports[i] (pucch_demodulator_format2.cpp:185): the two agree for the port list 0..P-1. All powers are
+ * linear; the caller takes 10 log10 and combines the ports as channel_estimate::get_channel_state_information does.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint16_t slot_index;         /* slot within the frame, < 10 << numerology */
+  uint8_t  numerology;         /* 0..4 */
+  uint8_t  cp_extended;        /* 0 normal, 1 extended (numerology 2 only) */
+  uint16_t starting_prb;       /* first grid PRB of the first (or only) hop */
+  uint16_t second_hop_prb;     /* first grid PRB of the second symbol; 0xffff: no intra-slot hopping */
+  uint8_t  nof_prb;            /* 1..16 */
+  uint8_t  start_symbol_index; /* start_symbol_index + nof_symbols <= 14 (12 with the extended CP) */
+  uint8_t  nof_symbols;        /* 1..2; hopping needs 2 */
+  uint8_t  nof_ports;          /* 1..4 */
+  uint16_t rnti;               /* scrambling: c_init = rnti 2^15 + n_id */
+  uint16_t n_id;               /* 0..1023 */
+  uint16_t n_id_0;             /* DM-RS scrambling identity, 0..65535 */
+  uint16_t nof_uci_bits;       /* HARQ-ACK + SR + CSI Part 1 bits, 3..1706; validation only */
+  uint8_t  ports[4];           /* grid ports, in the order of format2_configuration::ports */
+  uint32_t grid_index;         /* < nof_grids */
+  uint32_t llr_offset;         /* first of the PDU's 16 nof_prb nof_symbols LLRs in d_llrs; a multiple of 4 */
+} srsgpu_pucch_f2_config;
+
+/** One per PDU, in PDU order, 96 bytes, every byte written by every execute; entries of ports past nof_ports are 0. */
+typedef struct {
+  float  noise_var[4];      /* linear, already floored at rsrp / 10^10 */
+  float  rsrp[4];           /* linear */
+  float  epre[4];           /* linear */
+  float  cfo_hz[4];         /* NaN when no hop has two symbols; reported, never compensated */
+  double time_alignment[4]; /* seconds, a multiple of T_c: the mean of the hops */
+} srsgpu_pucch_f2_result;
+
+typedef struct srsgpu_pucch_f2_plan srsgpu_pucch_f2_plan;
+
+/** Refuses what pucch_pdu_validator_impl::is_valid and the estimator's and demodulator's assertions refuse (nof_prb
+ *  outside 1..16, symbols outside 1..2, hopping with one symbol, PRBs or symbols outside the grid or the slot, no
+ *  ports or more than the grid has, an effective code rate above 0.8 -- checked before the payload size, as there --
+ *  and a payload outside 3..1706 bits) and in addition: a port outside the grid or listed twice, a numerology, slot
+ *  index, cyclic prefix or n_id outside its range, a grid_index outside the grids, an llr_offset that is no multiple
+ *  of 4 and LLR ranges of two PDUs that overlap. A refused create leaves no live device buffer. Blocking. */
+int srsgpu_pucch_f2_plan_create(srsgpu_context*               ctx,
+                                const srsgpu_pucch_f2_config* pdus,
+                                uint32_t                      nof_pdus,
+                                uint32_t                      grid_nof_prb,
+                                uint32_t                      grid_nof_ports,
+                                uint32_t                      nof_grids,
+                                srsgpu_pucch_f2_plan**        plan);
+
+/** Processes every planned PDU: reads d_grids (uint32 per RE: re | im << 16, bf16; nof_grids x ports x 14 x 12 PRBs),
+ *  writes the PDUs' LLRs into d_llrs (nothing outside their ranges) and every byte of the nof_pdus results. One
+ *  launch, one workgroup per PDU, asynchronous on `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_pucch_f2_plan_execute(const srsgpu_pucch_f2_plan* plan,
+                                 const uint32_t*             d_grids,
+                                 int8_t*                     d_llrs,
+                                 srsgpu_pucch_f2_result*     d_results,
+                                 void*                       stream);
+
+void srsgpu_pucch_f2_plan_destroy(srsgpu_pucch_f2_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

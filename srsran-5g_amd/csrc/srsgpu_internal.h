@@ -752,6 +752,20 @@ void launch_srs_estimator(const srs_job*     d_jobs,
                           srsgpu_srs_result* d_results,
                           hipStream_t        stream);
 
+/// PUCCH Format 2 front end (pucch_f2.hip): one workgroup per job (pucch_f2_host.h: one PDU), the DM-RS symbols and the
+/// 128-entry twiddle table as (re, im) floats, 16 scrambling words per PDU, the LLRs at each job's offset and one
+/// srsgpu_pucch_f2_result per PDU.
+struct pucch_f2_job;
+void launch_pucch_f2(const pucch_f2_job*     d_jobs,
+                     uint32_t                nof_jobs,
+                     const float*            d_dmrs,
+                     const uint32_t*         d_scrambling,
+                     const float*            d_twiddles,
+                     const uint32_t*         d_grids,
+                     int8_t*                 d_llrs,
+                     srsgpu_pucch_f2_result* d_results,
+                     hipStream_t             stream);
+
 /// SS/PBCH blocks (ssb.hip): one block, one workgroup (ssb_host.h: the descriptors and the tables all blocks share).
 struct ssb_desc;
 struct ssb_tables;

@@ -500,6 +500,37 @@ SRS_RESULT_DTYPE = np.dtype([("channel", "<f4", (4, 4, 2)), ("time_alignment", "
 assert SRS_RESULT_DTYPE.itemsize == 192
 
 
+class PucchF2Config(ctypes.Structure):
+    """srsgpu_pucch_f2_config (include/srsgpu_phy.h): one PUCCH Format 2 PDU, PRBs as grid PRBs, second_hop_prb
+    PUCCH_NO_HOP without hopping, where its grid lies and where its 16 nof_prb nof_symbols LLRs go."""
+    _fields_ = [
+        ("slot_index", ctypes.c_uint16),
+        ("numerology", ctypes.c_uint8),
+        ("cp_extended", ctypes.c_uint8),
+        ("starting_prb", ctypes.c_uint16),
+        ("second_hop_prb", ctypes.c_uint16),
+        ("nof_prb", ctypes.c_uint8),
+        ("start_symbol_index", ctypes.c_uint8),
+        ("nof_symbols", ctypes.c_uint8),
+        ("nof_ports", ctypes.c_uint8),
+        ("rnti", ctypes.c_uint16),
+        ("n_id", ctypes.c_uint16),
+        ("n_id_0", ctypes.c_uint16),
+        ("nof_uci_bits", ctypes.c_uint16),
+        ("ports", ctypes.c_uint8 * 4),
+        ("grid_index", ctypes.c_uint32),
+        ("llr_offset", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(PucchF2Config) == 32
+# srsgpu_pucch_f2_result, 96 bytes per PDU: per listed port, powers linear, time alignment in seconds, CFO in Hz (NaN
+# when no hop has two symbols).
+PUCCH_F2_RESULT_DTYPE = np.dtype([("noise_var", "<f4", (4,)), ("rsrp", "<f4", (4,)), ("epre", "<f4", (4,)),
+                                  ("cfo_hz", "<f4", (4,)), ("time_alignment", "<f8", (4,))])
+assert PUCCH_F2_RESULT_DTYPE.itemsize == 96
+
+
 class PuschChestConfig(ctypes.Structure):
     """srsgpu_pusch_chest_config (include/srsgpu_phy.h): dmrs_pusch_estimator::configuration of one transmission."""
     _fields_ = [
@@ -661,6 +692,11 @@ def load_library(path: str = LIB_PATH):
     lib.srsgpu_srs_estimator_plan_execute.argtypes = [P, P, P, P]
     lib.srsgpu_srs_estimator_plan_destroy.argtypes = [P]
     lib.srsgpu_srs_estimator_plan_destroy.restype = None
+    lib.srsgpu_pucch_f2_plan_create.argtypes = [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.POINTER(P)]
+    lib.srsgpu_pucch_f2_plan_execute.argtypes = [P, P, P, P, P]
+    lib.srsgpu_pucch_f2_plan_destroy.argtypes = [P]
+    lib.srsgpu_pucch_f2_plan_destroy.restype = None
     lib.srsgpu_pusch_chest_plan_create_ex.argtypes = [P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.POINTER(P)]
     lib.srsgpu_pdsch_dmrs_plan_destroy.argtypes = [P]
@@ -750,6 +786,7 @@ EXPORTED_SYMBOLS = [
     "srsgpu_prach_detector_plan_create", "srsgpu_prach_detector_plan_execute", "srsgpu_prach_detector_plan_destroy",
     "srsgpu_prach_max_delay_samples",
     "srsgpu_srs_estimator_plan_create", "srsgpu_srs_estimator_plan_execute", "srsgpu_srs_estimator_plan_destroy",
+    "srsgpu_pucch_f2_plan_create", "srsgpu_pucch_f2_plan_execute", "srsgpu_pucch_f2_plan_destroy",
     "srsgpu_debug_live_device_buffers",
 ]
 
@@ -1842,6 +1879,216 @@ class PucchDetector:
             f1_out.append([one(raw[at + i], e[2]) for i, e in enumerate(r.entries)])
             at += len(r.entries)
         return f0_out, f1_out
+
+
+@dataclass
+class PucchF2:
+    """pucch_processor::format2_configuration of one PDU: grid PRBs (the BWP start added), second_hop_prb None without
+    hopping, `ports` the grid ports in order, and the payload as its three fields (CSI Part 2 is refused by the
+    reference). llr_offset None: the PDUs' LLRs follow one another."""
+    slot_index: int
+    starting_prb: int
+    nof_prb: int
+    start_symbol_index: int
+    nof_symbols: int
+    rnti: int
+    n_id: int
+    n_id_0: int
+    nof_harq_ack: int = 0
+    nof_sr: int = 0
+    nof_csi_part1: int = 0
+    ports: Sequence[int] = (0,)
+    second_hop_prb: Optional[int] = None
+    numerology: int = 1
+    cp_extended: int = 0
+    grid_index: int = 0
+    llr_offset: Optional[int] = None
+
+    @property
+    def nof_uci_bits(self) -> int:
+        return self.nof_harq_ack + self.nof_sr + self.nof_csi_part1
+
+    @property
+    def nof_llrs(self) -> int:
+        return 16 * self.nof_prb * self.nof_symbols
+
+
+def make_pucch_f2_configs(pdus: Sequence[PucchF2]):
+    """The C array of srsgpu_pucch_f2_plan_create and the LLR offsets used (a PDU without one follows the PDU before
+    it; 16 nof_prb nof_symbols is a multiple of 4)."""
+    cfg = (PucchF2Config * max(len(pdus), 1))()
+    offsets, o = [], 0
+    for a, d in zip(cfg, pdus):
+        a.slot_index, a.numerology, a.cp_extended = d.slot_index, d.numerology, d.cp_extended
+        a.starting_prb = d.starting_prb
+        a.second_hop_prb = PUCCH_NO_HOP if d.second_hop_prb is None else d.second_hop_prb
+        a.nof_prb, a.start_symbol_index, a.nof_symbols, a.nof_ports = d.nof_prb, d.start_symbol_index, d.nof_symbols, len(d.ports)
+        a.rnti, a.n_id, a.n_id_0, a.nof_uci_bits = d.rnti, d.n_id, d.n_id_0, d.nof_uci_bits
+        for i, p in enumerate(list(d.ports)[:4]):
+            a.ports[i] = p
+        a.grid_index = d.grid_index
+        a.llr_offset = o if d.llr_offset is None else d.llr_offset
+        offsets.append(int(a.llr_offset))
+        o = int(a.llr_offset) + max(d.nof_llrs, 0)
+    return cfg, offsets
+
+
+class PucchF2Plan(_Handle):
+    """srsgpu_pucch_f2_plan: estimation, equalisation, demapping and descrambling of every Format 2 PDU of a batch of
+    slots in one launch. Results: one PUCCH_F2_RESULT_DTYPE record per PDU. Raises SrsGpuError on a refusal."""
+    _destroy = "srsgpu_pucch_f2_plan_destroy"
+
+    def __init__(self, ctx: Context, pdus: Sequence[PucchF2], grid_nof_prb: int, grid_nof_ports: int = 4,
+                 nof_grids: Optional[int] = None):
+        self.ctx = ctx
+        if nof_grids is None:
+            nof_grids = max([d.grid_index for d in pdus], default=0) + 1
+        self.nof_grids, self.grid_nof_prb, self.grid_nof_ports = nof_grids, grid_nof_prb, grid_nof_ports
+        cfg, self.llr_offsets = make_pucch_f2_configs(pdus)
+        self.nof_pdus = len(pdus)
+        self.nof_llrs = max([o + d.nof_llrs for o, d in zip(self.llr_offsets, pdus)], default=0)
+        h = ctypes.c_void_p()
+        _check(load_library().srsgpu_pucch_f2_plan_create(ctx.handle, ctypes.cast(cfg, ctypes.c_void_p), len(pdus),
+                                                          grid_nof_prb, grid_nof_ports, nof_grids, ctypes.byref(h)))
+        self.handle = h
+
+    def execute(self, d_grids, d_llrs, d_results, stream=None):
+        """d_grids: (nof_grids, ports, 14, 12 PRBs) int32 / uint32 words (re | im << 16, bf16); d_llrs: int8, at least
+        nof_llrs entries, written only inside the PDUs' ranges; d_results: at least 96 * nof_pdus bytes, every byte of
+        which is written. Asynchronous on `stream`."""
+        _check(_lib.srsgpu_pucch_f2_plan_execute(self.handle, _dptr(d_grids), _dptr(d_llrs), _dptr(d_results),
+                                                 _stream_handle(stream)))
+
+
+@dataclass
+class PucchF2Result:
+    """pucch_processor_result of one Format 2 PDU: the payload split in the reference's order (HARQ-ACK, SR, CSI
+    Part 1), the status (True = uci_status::valid) and the channel state, per port (linear, seconds, Hz) and combined as
+    channel_estimate::get_channel_state_information combines it (dB; cfo_hz NaN when no hop has two symbols)."""
+    harq_ack: np.ndarray
+    sr: np.ndarray
+    csi_part1: np.ndarray
+    valid: bool
+    noise_var: np.ndarray
+    rsrp: np.ndarray
+    epre: np.ndarray
+    time_alignment_ports: np.ndarray
+    cfo_hz_ports: np.ndarray
+    epre_dB: float
+    rsrp_dB: float
+    sinr_dB: float
+    time_alignment: float
+    cfo_hz: float
+
+    @property
+    def payload(self) -> np.ndarray:
+        return np.concatenate([self.harq_ack, self.sr, self.csi_part1]).astype(np.uint8)
+
+
+class PucchF2Batch:
+    """The three plans of a batch of Format 2 PDUs with their device buffers: launch(d_grids) enqueues the front end,
+    the short-block decoder (payloads of 3..11 bits, Qm 2) and the polar decoder (12 bits and more; E <= 512 never
+    reaches two codeblocks) on one stream, both decoders reading source 0 at the PDUs' LLR offsets; results() reads
+    them back. Allocation-free between the two, so launch() can be captured in a graph."""
+
+    def __init__(self, ctx: Context, pdus: Sequence[PucchF2], grid_nof_prb: int, grid_nof_ports: int = 4,
+                 nof_grids: Optional[int] = None):
+        self.ctx, self.pdus = ctx, list(pdus)
+        dev = torch.device("cuda", ctx.device)
+        self.front = PucchF2Plan(ctx, self.pdus, grid_nof_prb, grid_nof_ports, nof_grids)
+        offs = self.front.llr_offsets
+        self.short_ids = [i for i, d in enumerate(self.pdus) if d.nof_uci_bits <= 11]
+        self.polar_ids = [i for i, d in enumerate(self.pdus) if d.nof_uci_bits >= 12]
+        self.short = UciDecoderPlan(ctx, [(self.pdus[i].nof_uci_bits, 2, 0, self.pdus[i].nof_llrs, offs[i])
+                                          for i in self.short_ids]) if self.short_ids else None
+        self.polar = UciPolarDecoderPlan(ctx, [(self.pdus[i].nof_uci_bits, 0, self.pdus[i].nof_llrs, offs[i], None)
+                                               for i in self.polar_ids]) if self.polar_ids else None
+        self.d_llrs = torch.zeros(self.front.nof_llrs + 4, dtype=torch.int8, device=dev)
+        self.d_results = torch.zeros(PUCCH_F2_RESULT_DTYPE.itemsize * max(len(self.pdus), 1), dtype=torch.uint8, device=dev)
+        self.d_short_msgs = torch.zeros(max(len(self.short_ids), 1), dtype=torch.int16, device=dev)
+        self.d_short_status = torch.zeros(max(len(self.short_ids), 1), dtype=torch.uint8, device=dev)
+        self.d_polar_msgs = torch.zeros(max(self.polar.nof_msg_words if self.polar else 0, 1), dtype=torch.int32, device=dev)
+        self.d_polar_status = torch.zeros(max(len(self.polar_ids), 1), dtype=torch.uint8, device=dev)
+
+    def launch(self, d_grids, stream=None):
+        self.front.execute(d_grids, self.d_llrs, self.d_results, stream)
+        if self.short is not None:
+            self.short.execute(self.d_llrs, None, None, self.d_short_msgs, self.d_short_status, stream)
+        if self.polar is not None:
+            self.polar.execute(self.d_llrs, None, None, self.d_polar_msgs, self.d_polar_status, stream)
+
+    def raw(self):
+        """(LLRs int8, PUCCH_F2_RESULT_DTYPE records) as the front end left them."""
+        return (self.d_llrs.cpu().numpy()[: self.front.nof_llrs],
+                self.d_results.cpu().numpy().view(PUCCH_F2_RESULT_DTYPE)[: len(self.pdus)])
+
+    def results(self):
+        _, raw = self.raw()
+        bits, valid = [None] * len(self.pdus), [False] * len(self.pdus)
+        if self.short is not None:
+            msgs, status = self.d_short_msgs.cpu().numpy().view(np.uint16), self.d_short_status.cpu().numpy()
+            for k, i in enumerate(self.short_ids):
+                a = self.pdus[i].nof_uci_bits
+                bits[i], valid[i] = ((int(msgs[k]) >> np.arange(a)) & 1).astype(np.uint8), bool(status[k])
+        if self.polar is not None:
+            words, status = self.d_polar_msgs.cpu().numpy().view(np.uint32), self.d_polar_status.cpu().numpy()
+            for k, i in enumerate(self.polar_ids):
+                bits[i] = uci_polar_unpack(words, self.polar.msg_word_offsets[k], self.pdus[i].nof_uci_bits)
+                valid[i] = bool(status[k])
+        return [pucch_f2_result(d, b, v, r) for d, b, v, r in zip(self.pdus, bits, valid, raw)]
+
+    def close(self):
+        for plan in (self.front, self.short, self.polar):
+            if plan is not None:
+                plan.close()
+
+
+def _power_db(v):
+    v = float(v)
+    return float(10.0 * np.log10(v)) if v > 0 else float("-inf") if v == 0 else float("nan")
+
+
+def pucch_f2_result(pdu: PucchF2, bits, valid, record) -> PucchF2Result:
+    """One PUCCH_F2_RESULT_DTYPE record and the decoded payload as a PucchF2Result: the payload split into HARQ-ACK,
+    SR and CSI Part 1, and the ports combined as channel_estimate::get_channel_state_information does (mean EPRE and
+    RSRP; time alignment and CFO of the port with the best RSRP / noise variance, the first unless another is strictly
+    better, 1000 standing for a zero noise variance; SINR from the summed RSRP over the summed noise variance, 60 dB
+    when that sum is no normal number). The dB conversion happens here, on the host."""
+    P = len(pdu.ports)
+    nv, rsrp, epre = (np.asarray(record[k][:P], np.float32) for k in ("noise_var", "rsrp", "epre"))
+    ta, cfo = np.asarray(record["time_alignment"][:P]), np.asarray(record["cfo_hz"][:P])
+    best, best_snr = 0, np.float32(0)
+    for i in range(P):
+        snr = rsrp[i] / nv[i] if nv[i] != 0 else np.float32(1000)
+        if snr > best_snr:
+            best, best_snr = i, snr
+    nsum = np.float32(nv.sum(dtype=np.float32))
+    normal = np.isfinite(nsum) and abs(nsum) >= np.finfo(np.float32).tiny
+    sinr = float(rsrp.sum(dtype=np.float32) / nsum) if normal else 1e6
+    b = np.asarray(bits, np.uint8)
+    h, s = pdu.nof_harq_ack, pdu.nof_harq_ack + pdu.nof_sr
+    return PucchF2Result(b[:h], b[h:s], b[s:], bool(valid), nv, rsrp, epre, ta, cfo,
+                         _power_db(epre.mean(dtype=np.float32)), _power_db(rsrp.mean(dtype=np.float32)), _power_db(sinr),
+                         float(ta[best]), float(cfo[best]))
+
+
+class PucchF2Processor:
+    """GPU counterpart of pucch_processor::process(grid, format2_configuration) (pucch_processor_impl.cpp:145) for a
+    batch: process_batch(grids, pdus) returns one PucchF2Result per PDU. grids: (nof_grids, ports, 14, 12 PRBs) uint32
+    (re | im << 16, bf16)."""
+
+    def __init__(self, ctx: Context, grid_nof_prb: int, grid_nof_ports: int = 4):
+        self.ctx, self.grid_nof_prb, self.grid_nof_ports = ctx, grid_nof_prb, grid_nof_ports
+
+    def process_batch(self, grids: np.ndarray, pdus: Sequence[PucchF2]):
+        dev = torch.device("cuda", self.ctx.device)
+        batch = PucchF2Batch(self.ctx, pdus, self.grid_nof_prb, self.grid_nof_ports, grids.shape[0])
+        d_grids = torch.from_numpy(np.ascontiguousarray(grids).view(np.int32)).to(dev)
+        batch.launch(d_grids)
+        torch.cuda.synchronize(dev)
+        out = batch.results()
+        batch.close()
+        return out
 
 
 @dataclass

@@ -340,8 +340,25 @@ int srsgpu_pdsch_modulator_plan_create_ex(srsgpu_context*                ctx,
         d.w[p][l][1]    = used ? c.precoding[p][l][1] * amp : 0.f;
       }
     }
+    // The (port, layer) terms the wideband path computes: those whose weight is not (0, 0). A port with no such
+    // term, or a matrix without zeros, keeps every term (pdsch_modulator.hip, modulate_res).
+    uint32_t w_mask   = 0;
+    bool     zero_row = false;
+    for (int p = 0; p < c.nof_ports; ++p) {
+      uint32_t row = 0;
+      for (int l = 0; l < c.nof_layers; ++l) {
+        if (!(d.w[p][l][0] == 0.f && d.w[p][l][1] == 0.f)) {
+          row |= 1u << (p * 4 + l);
+        }
+      }
+      zero_row = zero_row || row == 0;
+      w_mask |= row;
+    }
+    const bool no_zeros = __builtin_popcount(w_mask) == c.nof_ports * c.nof_layers;
+    d.w_mask            = (zero_row || no_zeros) ? MOD_W_MASK_DENSE : w_mask;
     d.prg_sc = 0;
     if (x != nullptr && x->prg_size > 0) {
+      d.w_mask = MOD_W_MASK_DENSE;
       // Per-PRG weights, the same amplitude folding (precoding2 *= scaling, pdsch_modulator_impl.cpp:96).
       d.prg_sc = static_cast<uint16_t>(x->prg_size * 12u);
       d.prg_w  = static_cast<uint32_t>(prg_w.size());

@@ -145,6 +145,30 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t r, uint32_t M, int order
   return acc;
 }
 
+/// The same product r(x) M(x) mod g(x) (order 16 or 24) with the byte table T0[v] = v x^order mod g in LDS
+/// (crc_byte_lut, or T_0 of the slice-by-4 tables): r = r0 + r1 x^8 + r2 x^16 by bytes, so
+/// r M = r0 (x) M + r1 (x) (M x^8 mod g) + r2 (x) (M x^16 mod g) with (x) an unreduced 8 x 24-bit carry-less product
+/// (below 2^31). The three products share one Horner accumulator (one shift per bit position, a mask-and-add per byte
+/// and bit) and the sum is reduced once through T0: 24 x 3 + 8 VALU and three table reads instead of 24 reduce-and-add
+/// steps. M x^8 and M x^16 come from M by one T0 step each (no further loads of the power table, and the monomial
+/// powers of a message's last chunks need no special case).
+__device__ __forceinline__ uint32_t gf2_mulmod_bytes(uint32_t r, uint32_t M, int order, const uint32_t* T0)
+{
+  const uint32_t mask = (1u << order) - 1u;
+  const uint32_t M8   = ((M << 8) & mask) ^ T0[M >> (order - 8)];
+  const uint32_t M16  = ((M8 << 8) & mask) ^ T0[M8 >> (order - 8)];
+  uint32_t       acc  = 0;
+#pragma unroll
+  for (int b = 7; b >= 0; --b) {
+    // Bit b of each byte of r as a 0 / -1 mask (one v_bfe_i32 each).
+    const uint32_t s0 = static_cast<uint32_t>(static_cast<int32_t>(r << (31 - b)) >> 31);
+    const uint32_t s1 = static_cast<uint32_t>(static_cast<int32_t>(r << (23 - b)) >> 31);
+    const uint32_t s2 = static_cast<uint32_t>(static_cast<int32_t>(r << (15 - b)) >> 31);
+    acc               = (acc << 1) ^ (s0 & M) ^ (s1 & M8) ^ (s2 & M16);
+  }
+  return (acc & mask) ^ T0[acc >> order];
+}
+
 /// CRC of data[0..nbytes) (global or LDS) by chunks: every lane runs the byte-table CRC over CS-byte chunks, then
 /// moves each chunk remainder r to the end of the message: r(x) x^(8 (nbytes - end)) mod g, with the power read from
 /// the per-bit contribution table P of the message length L = 8 nbytes (P[j] = x^(order + L - 1 - j) mod g, so the
@@ -164,10 +188,13 @@ __device__ __forceinline__ uint32_t crc_step4(uint32_t r, uint32_t m, int order,
 }
 
 /// block_crc_chunks with the slice-by-4 tables T (T_0 is the byte table): whole 4-byte words of a chunk in one step
-/// each, a trailing partial word byte by byte. Same results.
+/// each, a trailing partial word byte by byte. Same results. `words`: the 4-byte aligned address of data(0) when the
+/// bytes are in memory: a whole chunk is then read as aligned words and byte-swapped instead of byte by byte (a
+/// partial last chunk takes the byte reads). The chunk remainders are moved by gf2_mulmod_bytes through T_0.
 template <int CS, typename Data>
-__device__ inline uint32_t block_crc_slice4(Data data, int nbytes, const uint32_t* P, int order, uint32_t g,
-                                            const uint32_t* T, uint32_t* red, bool have_m0 = false, uint32_t m0 = 0)
+__device__ inline uint32_t block_crc_slice4(Data data, int nbytes, const uint32_t* P, int order, const uint32_t* T,
+                                            uint32_t* red, bool have_m0 = false, uint32_t m0 = 0,
+                                            const uint32_t* words = nullptr)
 {
   static_assert(CS % 4 == 0, "whole words per chunk");
   const uint32_t mask = (1u << order) - 1u;
@@ -180,27 +207,39 @@ __device__ inline uint32_t block_crc_slice4(Data data, int nbytes, const uint32_
     const int      b1 = min(b0 + CS, nbytes);
     const int      j  = 8 * b1 + order - 1;
     const uint32_t M  = (have_m0 && c == c0) ? m0 : ((j < L) ? P[j] : (1u << (order + L - 1 - j)));
-    uint32_t       byte[CS];
+    uint32_t       rem = 0;
+    if (words != nullptr && b0 + CS <= b1) {
+      uint32_t word[CS / 4];
 #pragma unroll
-    for (int k = 0; k < CS; ++k) {
-      byte[k] = (b0 + k < b1) ? static_cast<uint32_t>(data(b0 + k)) : 0u;
-    }
-    uint32_t rem = 0;
+      for (int w = 0; w < CS / 4; ++w) {
+        word[w] = words[b0 / 4 + w];
+      }
 #pragma unroll
-    for (int w = 0; w < CS / 4; ++w) {
-      const int k = 4 * w;
-      if (b0 + k + 4 <= b1) {
-        rem = crc_step4(rem, (byte[k] << 24) | (byte[k + 1] << 16) | (byte[k + 2] << 8) | byte[k + 3], order, T);
-      } else {
+      for (int w = 0; w < CS / 4; ++w) {
+        rem = crc_step4(rem, __builtin_bswap32(word[w]), order, T);
+      }
+    } else {
+      uint32_t byte[CS];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (b0 + k + q < b1) {
-            rem = ((rem << 8) ^ T[((rem >> (order - 8)) ^ byte[k + q]) & 0xffu]) & mask;
+      for (int k = 0; k < CS; ++k) {
+        byte[k] = (b0 + k < b1) ? static_cast<uint32_t>(data(b0 + k)) : 0u;
+      }
+#pragma unroll
+      for (int w = 0; w < CS / 4; ++w) {
+        const int k = 4 * w;
+        if (b0 + k + 4 <= b1) {
+          rem = crc_step4(rem, (byte[k] << 24) | (byte[k + 1] << 16) | (byte[k + 2] << 8) | byte[k + 3], order, T);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (b0 + k + q < b1) {
+              rem = ((rem << 8) ^ T[((rem >> (order - 8)) ^ byte[k + q]) & 0xffu]) & mask;
+            }
           }
         }
       }
     }
-    acc ^= gf2_mulmod(rem, M, order, g);
+    acc ^= gf2_mulmod_bytes(rem, M, order, T);
   }
   acc = wave_xor(acc);
   if ((threadIdx.x % WAVE) == 0) {

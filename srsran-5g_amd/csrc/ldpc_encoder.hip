@@ -672,7 +672,7 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if ((tid + h * PK_THREADS) * TCS < nb) {
-        acc ^= gf2_mulmod(rem[h], tm[h], order, tcd.poly);
+        acc ^= gf2_mulmod_bytes(rem[h], tm[h], order, t4t);
       }
     }
     acc = wave_xor(acc);
@@ -687,7 +687,7 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
   } else if (carrier) {
     const uint8_t* tbp = tbs + tcd.byte_offset;
     tb_crc = block_crc_slice4<16>([tbp](int i) { return tbp[i]; }, static_cast<int>(tcd.nbytes),
-                                  crc_tables + tcd.table, static_cast<int>(tcd.order), tcd.poly, t4t, red);
+                                  crc_tables + tcd.table, static_cast<int>(tcd.order), t4t, red);
   }
   ENC_STAMP(1);
   if (carrier) {  // the TB CRC's bytes: message bytes [qc, nd8), at most three
@@ -703,7 +703,7 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
       __syncthreads();  // the TB CRC's bytes in msg
     }
     const uint32_t crc = block_crc_slice4<CB_CS>([](int q) { return msg[q]; }, cb_bytes, crc_tables + d.crc_table, 24,
-                                                 0x1800063u, t4b, red, pre_m, m0);
+                                                 t4b, red, pre_m, m0, reinterpret_cast<const uint32_t*>(msg));
     if (tid < 3) {
       msg[d.used / 8 + tid] = static_cast<uint8_t>(crc >> (16 - 8 * tid));
     }

@@ -75,7 +75,15 @@ __device__ __forceinline__ float2 constellation_point(uint32_t idx, uint32_t qm)
 /// The chunk's REs: modulation, layer mapping, precoding and mapping. MAP: general allocation (the plan's RE ->
 /// subcarrier map); PRG: per-PRG precoding weights (resource_grid_mapper_impl.cpp:218). points: the transmission's
 /// 2^Qm constellation points, staged in LDS by the workgroup (one LDS read per layer and RE).
-template <bool MAP, bool PRG>
+///
+/// SPARSE: the wideband weights have (0, 0) entries and the (port, layer) terms outside mod_desc::w_mask are skipped
+/// (W_DENSE: every term; W_MASK: the workgroup-uniform mask; W_IDENTITY4: four layers on four ports with a diagonal
+/// matrix, straight-line code). A skipped term is +/-0 and a kept one is never -0 (the constellation points are
+/// non-zero), so a sum with at least one kept term is the same bits; a port with no kept term would take the sign of
+/// its zero from the skipped terms, and such a transmission keeps W_DENSE (the plan's choice).
+enum { W_DENSE = 0, W_MASK = 1, W_IDENTITY4 = 2 };
+
+template <bool MAP, bool PRG, int SPARSE = W_DENSE>
 __device__ __forceinline__ void modulate_res(const mod_desc& d,
                                              const mod_chunk& ch,
                                              const uint32_t*  bits,
@@ -85,7 +93,9 @@ __device__ __forceinline__ void modulate_res(const mod_desc& d,
                                              uint32_t* __restrict__ grids)
 {
   const uint32_t tid = threadIdx.x;
-  const uint32_t qm = d.qm, L = d.L, P = d.P, Lq = L * qm;
+  static_assert(!PRG || SPARSE == W_DENSE, "the mask describes the wideband weights");
+  const uint32_t qm = d.qm, L = (SPARSE == W_IDENTITY4) ? 4u : d.L, P = (SPARSE == W_IDENTITY4) ? 4u : d.P, Lq = L * qm;
+  const uint32_t wmask = (SPARSE == W_IDENTITY4) ? MOD_W_MASK_IDENTITY4 : d.w_mask;
   const uint32_t qmask = (1u << qm) - 1u;
   float          w[4][4][2];
 #pragma unroll
@@ -151,15 +161,22 @@ __device__ __forceinline__ void modulate_res(const mod_desc& d,
     for (int p = 0; p < 4; ++p) {
       if (p < static_cast<int>(P)) {
         float sr = 0.f, si = 0.f;
+        bool  first = true;  // SPARSE: no kept term yet (workgroup-uniform)
 #pragma unroll
         for (int ly = 0; ly < 4; ++ly) {
-          if (ly < static_cast<int>(L)) {
+          if (ly < static_cast<int>(L) && (SPARSE == W_DENSE || ((wmask >> (p * 4 + ly)) & 1u) != 0)) {
             const float wr = PRG ? wt[(p * 4 + ly) * 2] : w[p][ly][0];
             const float wi = PRG ? wt[(p * 4 + ly) * 2 + 1] : w[p][ly][1];
             const float pr = xr[ly] * wr - xi[ly] * wi;
             const float pi = xr[ly] * wi + xi[ly] * wr;
-            sr             = (ly == 0) ? pr : sr + pr;
-            si             = (ly == 0) ? pi : si + pi;
+            if constexpr (SPARSE == W_DENSE) {
+              sr = (ly == 0) ? pr : sr + pr;
+              si = (ly == 0) ? pi : si + pi;
+            } else {
+              sr    = first ? pr : sr + pr;
+              si    = first ? pi : si + pi;
+              first = false;
+            }
           }
         }
         // (an unsigned 32-bit byte offset from the grid's SGPR base: saddr stores)
@@ -205,10 +222,24 @@ __global__ __launch_bounds__(MOD_THREADS) void pdsch_modulate_kernel(const mod_d
   // One instantiation per allocation kind, chosen per workgroup (uniform): the contiguous wideband path keeps its
   // weights in registers and its subcarrier arithmetic; the general path reads the RE -> subcarrier map and, with
   // PRGs, the PRG's weights.
+  // Wideband weights with zeros (mod_desc::w_mask): only the kept terms.
+  const uint32_t wmask = __builtin_amdgcn_readfirstlane(d.w_mask);
   if (d.sc_map == NO_SC_MAP) {
-    modulate_res<false, false>(d, ch, bits, points, sc_map, prg_w, grids);
+    if (wmask == MOD_W_MASK_DENSE) {
+      modulate_res<false, false>(d, ch, bits, points, sc_map, prg_w, grids);
+    } else if (wmask == MOD_W_MASK_IDENTITY4) {
+      modulate_res<false, false, W_IDENTITY4>(d, ch, bits, points, sc_map, prg_w, grids);
+    } else {
+      modulate_res<false, false, W_MASK>(d, ch, bits, points, sc_map, prg_w, grids);
+    }
   } else if (d.prg_sc == 0) {
-    modulate_res<true, false>(d, ch, bits, points, sc_map, prg_w, grids);
+    if (wmask == MOD_W_MASK_DENSE) {
+      modulate_res<true, false>(d, ch, bits, points, sc_map, prg_w, grids);
+    } else if (wmask == MOD_W_MASK_IDENTITY4) {
+      modulate_res<true, false, W_IDENTITY4>(d, ch, bits, points, sc_map, prg_w, grids);
+    } else {
+      modulate_res<true, false, W_MASK>(d, ch, bits, points, sc_map, prg_w, grids);
+    }
   } else {
     modulate_res<true, true>(d, ch, bits, points, sc_map, prg_w, grids);
   }

@@ -313,9 +313,16 @@ struct mod_desc {
   uint32_t seq_word_offset; ///< First word of the transmission's scrambling sequence in the plan's sequence buffer.
   uint32_t sc_map;          ///< General allocation: first entry of the RE -> grid subcarrier map (NO_SC_MAP: contiguous).
   uint32_t prg_w;           ///< Per-PRG precoding: first float of [prg][port][layer][2] (amplitude folded in).
-  uint32_t pad3[3];
+  uint32_t w_mask;          ///< Wideband weights: bit 4 p + l set where w[p][l] is not (0, 0), or MOD_W_MASK_DENSE.
+  uint32_t pad3[2];
 };
 static_assert(sizeof(mod_desc) == 224, "mod_desc layout");
+
+/// mod_desc::w_mask of a transmission whose every (port, layer) term is computed: no (0, 0) weight, a port whose
+/// weights are all (0, 0), or per-PRG weights.
+constexpr uint32_t MOD_W_MASK_DENSE = 0u;
+/// mod_desc::w_mask of four layers on four ports with a diagonal matrix.
+constexpr uint32_t MOD_W_MASK_IDENTITY4 = 0x8421u;
 
 /// mod_desc::sc_map of the contiguous fast path.
 constexpr uint32_t NO_SC_MAP = 0xffffffffu;

@@ -877,6 +877,83 @@ int srsgpu_pucch_f2_plan_execute(const srsgpu_pucch_f2_plan* plan,
 void srsgpu_pucch_f2_plan_destroy(srsgpu_pucch_f2_plan* plan);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH Format 3 / 4 front end — the part of srsran::pucch_processor::process(const resource_grid_reader&, const
+ * format3_configuration&) and (..., const format4_configuration&) (lib/phy/upper/channel_processors/pucch/
+ * pucch_processor_impl.cpp:227 / :315) in front of the UCI decoder: dmrs_pucch_estimator_formats3_4::estimate
+ * (lib/phy/upper/signal_processors/pucch/dmrs_pucch_estimator_formats3_4.cpp:94, over
+ * port_channel_estimator_average_impl with mean smoothing, the average time strategy and no CFO compensation:
+ * signal_processor_factories.cpp:146) and pucch_demodulator_format3 / format4::demodulate (ZF 1 x N per data symbol,
+ * the 12 nof_prb-point inverse DFT scaled by 1 / sqrt(12 nof_prb), the mean of the valid noise variances, Format 4's
+ * inverse block-wise spreading, QPSK or pi/2-BPSK soft demapping, descrambling), for every Format 3 and Format 4 PDU of
+ * a batch of slots in one launch, from bf16 grids of the uplink plans' layout to descrambled int8 LLRs and the per-port
+ * channel state. The LLRs lie where srsgpu_uci_decoder_plan (3..11 bits, Qm 1 or 2) and
+ * srsgpu_uci_polar_decoder_plan (12 bits and more) read them in place: E = 12 nof_prb n_data Qm for Format 3 and
+ * 12 n_data Qm / occ_length for Format 4 at llr_offset, n_data the symbols without DM-RS (TS 38.211 Table
+ * 6.4.1.3.3.2-1), Qm 1 with pi2_bpsk and 2 without.
+ *
+ * PRBs are grid PRBs (the BWP start already added). Group hopping is NEITHER in the reference's processor and no
+ * parameter here. Data REs and pilots of receive port i both come from grid port ports[i]
+ * (pucch_formats3_4_helpers.h:208), unlike Format 2. All powers are linear; the caller takes 10 log10 and combines the
+ * ports as channel_estimate::get_channel_state_information does. The result record is srsgpu_pucch_f2_result with its
+ * meaning unchanged; the time alignment is 0 for every port, which is what the reference reports under mean smoothing
+ * (its estimator sees one constant per hop).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint16_t slot_index;         /* slot within the frame, < 10 << numerology */
+  uint8_t  format;             /* 3 or 4 */
+  uint8_t  numerology;         /* 0..4 */
+  uint8_t  cp_extended;        /* 0 normal, 1 extended (numerology 2 only) */
+  uint8_t  nof_prb;            /* Format 3: 1..16 of the form 2^a 3^b 5^c; Format 4: 1 */
+  uint8_t  start_symbol_index; /* start_symbol_index + nof_symbols <= 14 (12 with the extended CP) */
+  uint8_t  nof_symbols;        /* 4..14 */
+  uint16_t starting_prb;       /* first grid PRB of the first (or only) hop */
+  uint16_t second_hop_prb;     /* first grid PRB from symbol nof_symbols / 2 on; 0xffff: no intra-slot hopping */
+  uint8_t  additional_dmrs;    /* 0 or 1: four DM-RS symbols for 10..14 symbols */
+  uint8_t  pi2_bpsk;           /* 0: QPSK, 1: pi/2-BPSK */
+  uint8_t  occ_length;         /* Format 4: 2 or 4; Format 3: ignored */
+  uint8_t  occ_index;          /* Format 4: < occ_length; Format 3: ignored */
+  uint16_t rnti;               /* scrambling: c_init = rnti 2^15 + n_id_scrambling */
+  uint16_t n_id_scrambling;    /* 0..1023 */
+  uint16_t n_id_hopping;       /* 0..1023: u = n_id_hopping mod 30 and the cyclic shift hopping n_cs */
+  uint16_t nof_uci_bits;       /* HARQ-ACK + SR + CSI Part 1 bits, 3..1706; validation only */
+  uint8_t  nof_ports;          /* 1..4 */
+  uint8_t  ports[4];           /* grid ports, in the order of formatN_configuration::ports */
+  uint8_t  reserved[3];        /* 0 */
+  uint32_t grid_index;         /* < nof_grids */
+  uint32_t llr_offset;         /* first of the PDU's E LLRs in d_llrs; a multiple of 4 (E itself need not be one) */
+} srsgpu_pucch_f34_config;
+
+typedef struct srsgpu_pucch_f34_plan srsgpu_pucch_f34_plan;
+
+/** Refuses what pucch_pdu_validator_impl::is_valid (pucch_processor_impl.cpp:616 / :703) refuses (PRBs or symbols
+ *  outside the grid or the slot, no ports or more than the grid has, an effective code rate above 0.8 -- checked
+ *  before the payload size, as there --, a payload outside 3..1706 bits, nof_prb outside 1..16, occ_length other than
+ *  2 or 4), what the demodulators and the transform precoder assert on (nof_symbols outside 4..14, a nof_prb that is no
+ *  2^a 3^b 5^c -- the validator admits 7, 11, 13 and 14 --, occ_index >= occ_length) and in addition: a format other
+ *  than 3 or 4, a Format 4 nof_prb other than 1, a port outside the grid or listed twice, a numerology, slot index,
+ *  cyclic prefix, flag or identity outside its range, a grid_index outside the grids, an llr_offset that is no
+ *  multiple of 4 and LLR ranges of two PDUs that overlap. A refused create leaves no live device buffer. Blocking. */
+int srsgpu_pucch_f34_plan_create(srsgpu_context*                ctx,
+                                 const srsgpu_pucch_f34_config* pdus,
+                                 uint32_t                       nof_pdus,
+                                 uint32_t                       grid_nof_prb,
+                                 uint32_t                       grid_nof_ports,
+                                 uint32_t                       nof_grids,
+                                 srsgpu_pucch_f34_plan**        plan);
+
+/** Processes every planned PDU: reads d_grids (uint32 per RE: re | im << 16, bf16; nof_grids x ports x 14 x 12 PRBs),
+ *  writes each PDU's E LLRs into d_llrs (4-byte aligned; nothing outside the ranges, whose tails are stored by bytes)
+ *  and every byte of the nof_pdus results (entries of ports past nof_ports are 0). One launch, one workgroup per PDU,
+ *  asynchronous on `stream`, allocation-free, hipGraph-capturable. */
+int srsgpu_pucch_f34_plan_execute(const srsgpu_pucch_f34_plan* plan,
+                                  const uint32_t*              d_grids,
+                                  int8_t*                      d_llrs,
+                                  srsgpu_pucch_f2_result*      d_results,
+                                  void*                        stream);
+
+void srsgpu_pucch_f34_plan_destroy(srsgpu_pucch_f34_plan* plan);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * OFDM slot modulator / demodulator — replace srsran::ofdm_slot_modulator::modulate(span<cf_t> output,
  * const resource_grid_reader& grid, unsigned port_index, unsigned slot_index)
  * (include/srsran/phy/lower/modulation/ofdm_modulator.h:100, lib/phy/lower/modulation/ofdm_modulator_impl.cpp:115,

@@ -139,6 +139,7 @@ struct plan_deleter {
   void operator()(srsgpu_prach_detector_plan* p) const { srsgpu_prach_detector_plan_destroy(p); }
   void operator()(srsgpu_srs_estimator_plan* p) const { srsgpu_srs_estimator_plan_destroy(p); }
   void operator()(srsgpu_pucch_f2_plan* p) const { srsgpu_pucch_f2_plan_destroy(p); }
+  void operator()(srsgpu_pucch_f34_plan* p) const { srsgpu_pucch_f34_plan_destroy(p); }
   void operator()(srsgpu_ofdm_plan* p) const { srsgpu_ofdm_plan_destroy(p); }
   void operator()(srsgpu_pusch_chest_plan* p) const { srsgpu_pusch_chest_plan_destroy(p); }
   void operator()(srsgpu_pusch_demodulator_plan* p) const { srsgpu_pusch_demodulator_plan_destroy(p); }

@@ -773,6 +773,20 @@ void launch_pucch_f2(const pucch_f2_job*     d_jobs,
                      srsgpu_pucch_f2_result* d_results,
                      hipStream_t             stream);
 
+/// PUCCH Format 3 / 4 front end (pucch_f34.hip): one workgroup per job (pucch_f34_host.h: one PDU), the DM-RS sequences
+/// and the roots of the inverse transforms as (re, im) floats, ceil(E / 32) scrambling words per PDU, the LLRs at each
+/// job's offset (d_llrs 4-byte aligned) and one srsgpu_pucch_f2_result per PDU.
+struct pucch_f34_job;
+void launch_pucch_f34(const pucch_f34_job*    d_jobs,
+                      uint32_t                nof_jobs,
+                      const float*            d_dmrs,
+                      const uint32_t*         d_scrambling,
+                      const float*            d_roots,
+                      const uint32_t*         d_grids,
+                      int8_t*                 d_llrs,
+                      srsgpu_pucch_f2_result* d_results,
+                      hipStream_t             stream);
+
 /// SS/PBCH blocks (ssb.hip): one block, one workgroup (ssb_host.h: the descriptors and the tables all blocks share).
 struct ssb_desc;
 struct ssb_tables;

@@ -531,6 +531,38 @@ PUCCH_F2_RESULT_DTYPE = np.dtype([("noise_var", "<f4", (4,)), ("rsrp", "<f4", (4
 assert PUCCH_F2_RESULT_DTYPE.itemsize == 96
 
 
+class PucchF34Config(ctypes.Structure):
+    """srsgpu_pucch_f34_config (include/srsgpu_phy.h): one PUCCH Format 3 or 4 PDU, PRBs as grid PRBs, second_hop_prb
+    PUCCH_NO_HOP without hopping, where its grid lies and where its E LLRs go."""
+    _fields_ = [
+        ("slot_index", ctypes.c_uint16),
+        ("format", ctypes.c_uint8),
+        ("numerology", ctypes.c_uint8),
+        ("cp_extended", ctypes.c_uint8),
+        ("nof_prb", ctypes.c_uint8),
+        ("start_symbol_index", ctypes.c_uint8),
+        ("nof_symbols", ctypes.c_uint8),
+        ("starting_prb", ctypes.c_uint16),
+        ("second_hop_prb", ctypes.c_uint16),
+        ("additional_dmrs", ctypes.c_uint8),
+        ("pi2_bpsk", ctypes.c_uint8),
+        ("occ_length", ctypes.c_uint8),
+        ("occ_index", ctypes.c_uint8),
+        ("rnti", ctypes.c_uint16),
+        ("n_id_scrambling", ctypes.c_uint16),
+        ("n_id_hopping", ctypes.c_uint16),
+        ("nof_uci_bits", ctypes.c_uint16),
+        ("nof_ports", ctypes.c_uint8),
+        ("ports", ctypes.c_uint8 * 4),
+        ("reserved", ctypes.c_uint8 * 3),
+        ("grid_index", ctypes.c_uint32),
+        ("llr_offset", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(PucchF34Config) == 40
+
+
 class PuschChestConfig(ctypes.Structure):
     """srsgpu_pusch_chest_config (include/srsgpu_phy.h): dmrs_pusch_estimator::configuration of one transmission."""
     _fields_ = [
@@ -697,6 +729,11 @@ def load_library(path: str = LIB_PATH):
     lib.srsgpu_pucch_f2_plan_execute.argtypes = [P, P, P, P, P]
     lib.srsgpu_pucch_f2_plan_destroy.argtypes = [P]
     lib.srsgpu_pucch_f2_plan_destroy.restype = None
+    lib.srsgpu_pucch_f34_plan_create.argtypes = [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.POINTER(P)]
+    lib.srsgpu_pucch_f34_plan_execute.argtypes = [P, P, P, P, P]
+    lib.srsgpu_pucch_f34_plan_destroy.argtypes = [P]
+    lib.srsgpu_pucch_f34_plan_destroy.restype = None
     lib.srsgpu_pusch_chest_plan_create_ex.argtypes = [P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       ctypes.POINTER(P)]
     lib.srsgpu_pdsch_dmrs_plan_destroy.argtypes = [P]
@@ -787,6 +824,7 @@ EXPORTED_SYMBOLS = [
     "srsgpu_prach_max_delay_samples",
     "srsgpu_srs_estimator_plan_create", "srsgpu_srs_estimator_plan_execute", "srsgpu_srs_estimator_plan_destroy",
     "srsgpu_pucch_f2_plan_create", "srsgpu_pucch_f2_plan_execute", "srsgpu_pucch_f2_plan_destroy",
+    "srsgpu_pucch_f34_plan_create", "srsgpu_pucch_f34_plan_execute", "srsgpu_pucch_f34_plan_destroy",
     "srsgpu_debug_live_device_buffers",
 ]
 
@@ -2083,6 +2121,194 @@ class PucchF2Processor:
     def process_batch(self, grids: np.ndarray, pdus: Sequence[PucchF2]):
         dev = torch.device("cuda", self.ctx.device)
         batch = PucchF2Batch(self.ctx, pdus, self.grid_nof_prb, self.grid_nof_ports, grids.shape[0])
+        d_grids = torch.from_numpy(np.ascontiguousarray(grids).view(np.int32)).to(dev)
+        batch.launch(d_grids)
+        torch.cuda.synchronize(dev)
+        out = batch.results()
+        batch.close()
+        return out
+
+
+def pucch_f34_dmrs_symbols(nof_symbols: int, hopping: bool, additional_dmrs: bool):
+    """TS 38.211 Table 6.4.1.3.3.2-1: the allocated symbols (0 = the first) of a Format 3 / 4 PDU that carry DM-RS."""
+    if nof_symbols == 4:
+        return (0, 2) if hopping else (1,)
+    two = {5: (0, 3), 6: (1, 4), 7: (1, 4), 8: (1, 5), 9: (1, 6), 10: (2, 7), 11: (2, 7), 12: (2, 8), 13: (2, 9),
+           14: (3, 10)}
+    four = {10: (1, 3, 6, 8), 11: (1, 3, 6, 9), 12: (1, 4, 7, 10), 13: (1, 4, 7, 11), 14: (1, 5, 8, 12)}
+    if additional_dmrs and nof_symbols in four:
+        return four[nof_symbols]
+    return two.get(nof_symbols, ())
+
+
+@dataclass
+class PucchF3:
+    """pucch_processor::format3_configuration of one PDU: grid PRBs (the BWP start added), second_hop_prb None without
+    hopping, `ports` the grid ports in order, and the payload as its three fields (CSI Part 2 is refused by the
+    reference). llr_offset None: the PDU's LLRs follow the PDU before it at the next multiple of 4."""
+    slot_index: int
+    starting_prb: int
+    nof_prb: int
+    start_symbol_index: int
+    nof_symbols: int
+    rnti: int
+    n_id_scrambling: int
+    n_id_hopping: int
+    nof_harq_ack: int = 0
+    nof_sr: int = 0
+    nof_csi_part1: int = 0
+    ports: Sequence[int] = (0,)
+    second_hop_prb: Optional[int] = None
+    additional_dmrs: bool = False
+    pi2_bpsk: bool = False
+    numerology: int = 1
+    cp_extended: int = 0
+    grid_index: int = 0
+    llr_offset: Optional[int] = None
+    format = 3
+    occ_length = 0
+    occ_index = 0
+
+    @property
+    def nof_uci_bits(self) -> int:
+        return self.nof_harq_ack + self.nof_sr + self.nof_csi_part1
+
+    @property
+    def modulation_order(self) -> int:
+        return 1 if self.pi2_bpsk else 2
+
+    @property
+    def nof_data_symbols(self) -> int:
+        return self.nof_symbols - len(pucch_f34_dmrs_symbols(self.nof_symbols, self.second_hop_prb is not None,
+                                                             self.additional_dmrs))
+
+    @property
+    def nof_llrs(self) -> int:
+        return 12 * self.nof_prb * self.nof_data_symbols * self.modulation_order
+
+
+@dataclass
+class PucchF4:
+    """pucch_processor::format4_configuration of one PDU (one PRB); see PucchF3. occ_length is the spreading factor."""
+    slot_index: int
+    starting_prb: int
+    start_symbol_index: int
+    nof_symbols: int
+    rnti: int
+    n_id_scrambling: int
+    n_id_hopping: int
+    occ_length: int
+    occ_index: int
+    nof_harq_ack: int = 0
+    nof_sr: int = 0
+    nof_csi_part1: int = 0
+    ports: Sequence[int] = (0,)
+    second_hop_prb: Optional[int] = None
+    additional_dmrs: bool = False
+    pi2_bpsk: bool = False
+    numerology: int = 1
+    cp_extended: int = 0
+    grid_index: int = 0
+    llr_offset: Optional[int] = None
+    format = 4
+    nof_prb = 1
+
+    nof_uci_bits = PucchF3.nof_uci_bits
+    modulation_order = PucchF3.modulation_order
+    nof_data_symbols = PucchF3.nof_data_symbols
+
+    @property
+    def nof_llrs(self) -> int:
+        return 12 * self.nof_data_symbols * self.modulation_order // max(self.occ_length, 1)
+
+
+def make_pucch_f34_configs(pdus):
+    """The C array of srsgpu_pucch_f34_plan_create and the LLR offsets used (a PDU without one follows the PDU before
+    it, at the next multiple of 4: E need not be one)."""
+    cfg = (PucchF34Config * max(len(pdus), 1))()
+    offsets, o = [], 0
+    for a, d in zip(cfg, pdus):
+        a.slot_index, a.format, a.numerology, a.cp_extended = d.slot_index, d.format, d.numerology, d.cp_extended
+        a.nof_prb, a.start_symbol_index, a.nof_symbols = d.nof_prb, d.start_symbol_index, d.nof_symbols
+        a.starting_prb = d.starting_prb
+        a.second_hop_prb = PUCCH_NO_HOP if d.second_hop_prb is None else d.second_hop_prb
+        a.additional_dmrs, a.pi2_bpsk = int(d.additional_dmrs), int(d.pi2_bpsk)
+        a.occ_length, a.occ_index = d.occ_length, d.occ_index
+        a.rnti, a.n_id_scrambling, a.n_id_hopping = d.rnti, d.n_id_scrambling, d.n_id_hopping
+        a.nof_uci_bits, a.nof_ports = d.nof_uci_bits, len(d.ports)
+        for i, p in enumerate(list(d.ports)[:4]):
+            a.ports[i] = p
+        a.grid_index = d.grid_index
+        a.llr_offset = o if d.llr_offset is None else d.llr_offset
+        offsets.append(int(a.llr_offset))
+        o = (int(a.llr_offset) + max(d.nof_llrs, 0) + 3) // 4 * 4
+    return cfg, offsets
+
+
+class PucchF34Plan(_Handle):
+    """srsgpu_pucch_f34_plan: estimation, equalisation, the inverse DFT, despreading, demapping and descrambling of
+    every Format 3 and Format 4 PDU of a batch of slots in one launch. Results: one PUCCH_F2_RESULT_DTYPE record per
+    PDU. Raises SrsGpuError on a refusal."""
+    _destroy = "srsgpu_pucch_f34_plan_destroy"
+
+    def __init__(self, ctx: Context, pdus, grid_nof_prb: int, grid_nof_ports: int = 4, nof_grids: Optional[int] = None):
+        self.ctx = ctx
+        if nof_grids is None:
+            nof_grids = max([d.grid_index for d in pdus], default=0) + 1
+        self.nof_grids, self.grid_nof_prb, self.grid_nof_ports = nof_grids, grid_nof_prb, grid_nof_ports
+        cfg, self.llr_offsets = make_pucch_f34_configs(pdus)
+        self.nof_pdus = len(pdus)
+        self.nof_llrs = max([o + max(d.nof_llrs, 0) for o, d in zip(self.llr_offsets, pdus)], default=0)
+        h = ctypes.c_void_p()
+        _check(load_library().srsgpu_pucch_f34_plan_create(ctx.handle, ctypes.cast(cfg, ctypes.c_void_p), len(pdus),
+                                                           grid_nof_prb, grid_nof_ports, nof_grids, ctypes.byref(h)))
+        self.handle = h
+
+    def execute(self, d_grids, d_llrs, d_results, stream=None):
+        """d_grids: (nof_grids, ports, 14, 12 PRBs) int32 / uint32 words (re | im << 16, bf16); d_llrs: int8, 4-byte
+        aligned, at least nof_llrs entries, written only inside the PDUs' ranges; d_results: at least 96 * nof_pdus
+        bytes, every byte of which is written. Asynchronous on `stream`."""
+        _check(_lib.srsgpu_pucch_f34_plan_execute(self.handle, _dptr(d_grids), _dptr(d_llrs), _dptr(d_results),
+                                                  _stream_handle(stream)))
+
+
+class PucchF34Batch(PucchF2Batch):
+    """The three plans of a batch of Format 3 / 4 PDUs with their device buffers, as PucchF2Batch: launch(d_grids)
+    enqueues the front end, the short-block decoder (3..11 bits, modulation order 1 with pi/2-BPSK and 2 without) and
+    the polar decoder (12 bits and more; a field of E >= 1088 with >= 360 bits takes two codeblocks there) on one
+    stream, both decoders reading source 0 at the PDUs' LLR offsets; results() reads them back."""
+
+    def __init__(self, ctx: Context, pdus, grid_nof_prb: int, grid_nof_ports: int = 4, nof_grids: Optional[int] = None):
+        self.ctx, self.pdus = ctx, list(pdus)
+        dev = torch.device("cuda", ctx.device)
+        self.front = PucchF34Plan(ctx, self.pdus, grid_nof_prb, grid_nof_ports, nof_grids)
+        offs = self.front.llr_offsets
+        self.short_ids = [i for i, d in enumerate(self.pdus) if d.nof_uci_bits <= 11]
+        self.polar_ids = [i for i, d in enumerate(self.pdus) if d.nof_uci_bits >= 12]
+        self.short = UciDecoderPlan(ctx, [(self.pdus[i].nof_uci_bits, self.pdus[i].modulation_order, 0,
+                                           self.pdus[i].nof_llrs, offs[i]) for i in self.short_ids]) if self.short_ids else None
+        self.polar = UciPolarDecoderPlan(ctx, [(self.pdus[i].nof_uci_bits, 0, self.pdus[i].nof_llrs, offs[i], None)
+                                               for i in self.polar_ids]) if self.polar_ids else None
+        self.d_llrs = torch.zeros(self.front.nof_llrs + 4, dtype=torch.int8, device=dev)
+        self.d_results = torch.zeros(PUCCH_F2_RESULT_DTYPE.itemsize * max(len(self.pdus), 1), dtype=torch.uint8, device=dev)
+        self.d_short_msgs = torch.zeros(max(len(self.short_ids), 1), dtype=torch.int16, device=dev)
+        self.d_short_status = torch.zeros(max(len(self.short_ids), 1), dtype=torch.uint8, device=dev)
+        self.d_polar_msgs = torch.zeros(max(self.polar.nof_msg_words if self.polar else 0, 1), dtype=torch.int32, device=dev)
+        self.d_polar_status = torch.zeros(max(len(self.polar_ids), 1), dtype=torch.uint8, device=dev)
+
+
+class PucchF34Processor:
+    """GPU counterpart of pucch_processor::process(grid, format3_configuration) and (grid, format4_configuration)
+    (pucch_processor_impl.cpp:227 / :315) for a batch: process_batch(grids, pdus) returns one PucchF2Result per PDU
+    (PucchF3 or PucchF4): the payload split into HARQ-ACK, SR and CSI Part 1, the status and the channel state combined
+    as for Format 2. grids: (nof_grids, ports, 14, 12 PRBs) uint32 (re | im << 16, bf16)."""
+
+    def __init__(self, ctx: Context, grid_nof_prb: int, grid_nof_ports: int = 4):
+        self.ctx, self.grid_nof_prb, self.grid_nof_ports = ctx, grid_nof_prb, grid_nof_ports
+
+    def process_batch(self, grids: np.ndarray, pdus):
+        dev = torch.device("cuda", self.ctx.device)
+        batch = PucchF34Batch(self.ctx, pdus, self.grid_nof_prb, self.grid_nof_ports, grids.shape[0])
         d_grids = torch.from_numpy(np.ascontiguousarray(grids).view(np.int32)).to(dev)
         batch.launch(d_grids)
         torch.cuda.synchronize(dev)

@@ -29,16 +29,10 @@ int srsgpu_csi_rs_plan_create(srsgpu_context*             ctx,
                               uint32_t                    nof_grids,
                               srsgpu_csi_rs_plan**        plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (cfgs == nullptr && nof_signals > 0)) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
-  }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
+  if (const int err = check_grid_args(ctx, plan_out, cfgs, nof_signals, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   const uint32_t nsc = 12 * grid_nof_prb, port_stride = 14 * nsc;
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * port_stride > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
-  }
   std::vector<csi_rs_job> jobs;
   // (grid, symbol, RB) -> the subcarriers of the RB that are written and the signal that wrote last, for the overlap check.
   std::unordered_map<uint64_t, std::pair<uint32_t, uint32_t>> owner;

@@ -32,6 +32,23 @@ inline int fail(int code, const char* fmt, ...)
   return code;
 }
 
+/// What every *_plan_create over resource grids checks first: its pointers (items may be null when there are none),
+/// the grid's size, and that nof_grids grids stay below 2^32 resource elements. SRSGPU_OK or the code of fail().
+inline int check_grid_args(const void* ctx, const void* plan_out, const void* items, uint32_t nof_items,
+                           uint32_t grid_nof_prb, uint32_t grid_nof_ports, uint32_t nof_grids)
+{
+  if (ctx == nullptr || plan_out == nullptr || (items == nullptr && nof_items > 0)) {
+    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
+  }
+  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
+    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
+  }
+  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * 14 * 12 * grid_nof_prb > 0xffffffffull) {
+    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
+  }
+  return SRSGPU_OK;
+}
+
 #define HIP_TRY(expr)                                                                                                  \
   do {                                                                                                                 \
     hipError_t err_ = (expr);                                                                                          \

@@ -58,16 +58,10 @@ int srsgpu_pdcch_plan_create(srsgpu_context*            ctx,
                              uint32_t                   nof_grids,
                              srsgpu_pdcch_plan**        plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (cfgs == nullptr && nof_dcis > 0)) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
-  }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
+  if (const int err = check_grid_args(ctx, plan_out, cfgs, nof_dcis, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   const uint32_t nsc = 12 * grid_nof_prb, port_stride = 14 * nsc;
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * port_stride > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
-  }
   const std::vector<uint32_t>                       crc_w = crc24c_weights();
   std::vector<pdcch_desc>                           descs(nof_dcis);
   std::vector<pdcch_code_desc>                      codes;

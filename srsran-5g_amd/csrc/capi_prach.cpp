@@ -2,6 +2,7 @@
 // leaves undefined, builds one job per (occasion, root sequence) (prach_host.cpp), computes one root-sequence row per
 // distinct (L, u) in double and uploads jobs, rows and twiddles. Everything on the device is prach_detector.hip.
 #include "capi_internal.h"
+#include "host_util.h"
 #include "prach_host.h"
 #include <map>
 #include <vector>
@@ -66,7 +67,7 @@ int srsgpu_prach_detector_plan_create(srsgpu_context*              ctx,
   plan_ptr<srsgpu_prach_detector_plan> plan(new srsgpu_prach_detector_plan());
   plan->ctx      = ctx;
   plan->nof_jobs = static_cast<uint32_t>(jobs.size());
-  if (!plan->d_jobs.upload(jobs) || !plan->d_roots.upload(rows) || !plan->d_twiddles.upload(prach_twiddles(PRACH_LONG_N))) {
+  if (!plan->d_jobs.upload(jobs) || !plan->d_roots.upload(rows) || !plan->d_twiddles.upload(unit_roots(PRACH_LONG_N))) {
     return fail(SRSGPU_ERR_HIP, "failed to upload the PRACH detector tables");
   }
   *plan_out = plan.release();

@@ -34,15 +34,11 @@ int srsgpu_pucch_detector_plan_create(srsgpu_context*                 ctx,
                                       uint32_t                        nof_grids,
                                       srsgpu_pucch_detector_plan**    plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (f0 == nullptr && nof_f0 > 0) || (f1_resources == nullptr && nof_f1 > 0) ||
-      (f1_entries == nullptr && nof_entries > 0)) {
+  if ((f1_resources == nullptr && nof_f1 > 0) || (f1_entries == nullptr && nof_entries > 0)) {
     return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
   }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
-  }
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * 14 * 12 * grid_nof_prb > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
+  if (const int err = check_grid_args(ctx, plan_out, f0, nof_f0, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   std::vector<pucch_job> jobs;
   std::vector<uint32_t>  entry_words(nof_entries, 0);

@@ -2,6 +2,7 @@
 // refuse and what they leave undefined, builds one job per PDU (pucch_f2_host.cpp) with its DM-RS symbols and scrambling
 // words and uploads jobs and tables. Everything on the device is pucch_f2.hip.
 #include "capi_internal.h"
+#include "host_util.h"
 #include "pucch_f2_host.h"
 #include <vector>
 
@@ -29,14 +30,8 @@ int srsgpu_pucch_f2_plan_create(srsgpu_context*               ctx,
                                 uint32_t                      nof_grids,
                                 srsgpu_pucch_f2_plan**        plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (pdus == nullptr && nof_pdus > 0)) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
-  }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
-  }
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * 14 * 12 * grid_nof_prb > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
+  if (const int err = check_grid_args(ctx, plan_out, pdus, nof_pdus, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   std::vector<pucch_f2_job> jobs;
   std::vector<float>        dmrs;
@@ -69,7 +64,7 @@ int srsgpu_pucch_f2_plan_create(srsgpu_context*               ctx,
   plan->ctx      = ctx;
   plan->nof_jobs = static_cast<uint32_t>(jobs.size());
   if (!plan->d_jobs.upload(jobs) || !plan->d_dmrs.upload(dmrs) || !plan->d_scrambling.upload(scrambling) ||
-      !plan->d_twiddles.upload(pucch_f2_twiddles())) {
+      !plan->d_twiddles.upload(unit_roots(PUCCH_F2_DFT))) {
     return fail(SRSGPU_ERR_HIP, "failed to upload the PUCCH Format 2 tables");
   }
   *plan_out = plan.release();

@@ -3,6 +3,7 @@
 // sequences and scrambling words, one table of roots per transform size in use, and uploads jobs and tables.
 // Everything on the device is pucch_f34.hip.
 #include "capi_internal.h"
+#include "host_util.h"
 #include "pucch_f34_host.h"
 #include <vector>
 
@@ -29,14 +30,8 @@ int srsgpu_pucch_f34_plan_create(srsgpu_context*                ctx,
                                  uint32_t                       nof_grids,
                                  srsgpu_pucch_f34_plan**        plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (pdus == nullptr && nof_pdus > 0)) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
-  }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
-  }
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * 14 * 12 * grid_nof_prb > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
+  if (const int err = check_grid_args(ctx, plan_out, pdus, nof_pdus, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   std::vector<pucch_f34_job> jobs;
   std::vector<float>         dmrs, roots;
@@ -53,7 +48,7 @@ int srsgpu_pucch_f34_plan_create(srsgpu_context*                ctx,
       return fail(SRSGPU_ERR_INVALID_ARG, "PUCCH Format 3/4 PDU %u: %s", i, why.c_str());
     }
     if (root_row[c.nof_prb] == 0xffffffffu) {
-      const std::vector<float> t = pucch_f34_roots(12u * c.nof_prb);
+      const std::vector<float> t = unit_roots(12u * c.nof_prb);
       root_row[c.nof_prb]        = static_cast<uint32_t>(roots.size() / 2);
       roots.insert(roots.end(), t.begin(), t.end());
     }

@@ -3,6 +3,7 @@
 // (u, L, cyclic shift / n_cs_max) in double and uploads jobs, rows and the phase table. Everything on the device is
 // srs_estimator.hip.
 #include "capi_internal.h"
+#include "host_util.h"
 #include "srs_host.h"
 #include <map>
 #include <tuple>
@@ -31,14 +32,8 @@ int srsgpu_srs_estimator_plan_create(srsgpu_context*             ctx,
                                      uint32_t                    nof_grids,
                                      srsgpu_srs_estimator_plan** plan_out)
 {
-  if (ctx == nullptr || plan_out == nullptr || (resources == nullptr && nof_resources > 0)) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "null argument");
-  }
-  if (grid_nof_prb < 1 || grid_nof_prb > 275 || grid_nof_ports < 1 || grid_nof_ports > 4) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "grid of %u PRBs x %u ports is outside 1..275 x 1..4", grid_nof_prb, grid_nof_ports);
-  }
-  if (static_cast<uint64_t>(nof_grids) * grid_nof_ports * 14 * 12 * grid_nof_prb > 0xffffffffull) {
-    return fail(SRSGPU_ERR_INVALID_ARG, "%u grids exceed 2^32 resource elements", nof_grids);
+  if (const int err = check_grid_args(ctx, plan_out, resources, nof_resources, grid_nof_prb, grid_nof_ports, nof_grids)) {
+    return err;
   }
   std::vector<srs_job>                                         jobs;
   std::vector<float>                                           rows;
@@ -77,7 +72,7 @@ int srsgpu_srs_estimator_plan_create(srsgpu_context*             ctx,
   plan_ptr<srsgpu_srs_estimator_plan> plan(new srsgpu_srs_estimator_plan());
   plan->ctx      = ctx;
   plan->nof_jobs = static_cast<uint32_t>(jobs.size());
-  if (!plan->d_jobs.upload(jobs) || !plan->d_seqs.upload(rows) || !plan->d_cexp.upload(srs_cexp_table())) {
+  if (!plan->d_jobs.upload(jobs) || !plan->d_seqs.upload(rows) || !plan->d_cexp.upload(unit_roots(SRS_CEXP_SIZE))) {
     return fail(SRSGPU_ERR_HIP, "failed to upload the SRS estimator tables");
   }
   *plan_out = plan.release();

@@ -1,23 +1,11 @@
 // Refusals and RE layout of the NZP-CSI-RS plan; see csi_rs_host.h.
 #include "csi_rs_host.h"
+#include "host_util.h"
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 namespace srsgpu {
 
 namespace {
-
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
 
 /// TS 38.211 Table 7.4.1.5.3-1, rows 1-5: ports, the k_0 values that keep the row's REs inside the RB, whether
 /// density 3 / 1 / 0.5 is allowed, and the CDM type.

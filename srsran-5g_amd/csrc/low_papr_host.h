@@ -1,6 +1,6 @@
 // The low-PAPR base sequence of TS 38.211 section 5.2.2 for host code: the PUSCH estimator's transform-precoded DM-RS
-// (capi_pusch_chest.cpp) and the SRS estimator's sequences (srs_host.cpp). No HIP call and no HIP type, so that a
-// host-only program can use it.
+// (capi_pusch_chest.cpp), the SRS estimator's sequences (srs_host.cpp) and the PUCCH Format 3 / 4 DM-RS
+// (pucch_f34_host.cpp). No HIP call and no HIP type, so that a host-only program can use it.
 //
 // Reference (behaviour, not code): lib/phy/upper/sequence_generators/low_papr_sequence_generator_impl.cpp:176 / :194.
 #pragma once
@@ -72,6 +72,27 @@ inline bool low_papr_sequence(unsigned u, unsigned m, std::vector<C>& out)
     out.push_back(v);
   }
   return true;
+}
+
+/// The sequence with a cyclic shift, r(n) e^{j 2 pi step n / 24}, n = 0..m-1, as (re, im) floats evaluated in double: the
+/// shift in 24ths of a turn, the resolution of the reference's table (low_papr_sequence_generator_impl.cpp:243). Empty
+/// for a length the specification does not define.
+inline std::vector<float> low_papr_shifted_sequence(unsigned u, unsigned m, uint64_t step)
+{
+  std::vector<int>   arg;
+  unsigned           nzc = 4;
+  std::vector<float> out;
+  if (!low_papr_argument(u, m, arg, nzc)) {
+    return out;
+  }
+  out.reserve(2 * static_cast<size_t>(m));
+  for (unsigned n = 0; n < m; ++n) {
+    const double a = 3.14159265358979323846 * static_cast<double>(arg[n]) / static_cast<double>(nzc) +
+                     2.0 * 3.14159265358979323846 * static_cast<double>((n * step) % 24u) / 24.0;
+    out.push_back(static_cast<float>(std::cos(a)));
+    out.push_back(static_cast<float>(std::sin(a)));
+  }
+  return out;
 }
 
 } // namespace srsgpu

@@ -1,26 +1,14 @@
 // CCE to PRB mapping and refusals of the PDCCH plan; see pdcch_host.h.
 #include "pdcch_host.h"
+#include "host_util.h"
 #include "polar_code.h"
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 namespace srsgpu {
 
 namespace {
 
 constexpr uint32_t REG_PER_CCE = 6, RB_PER_RESOURCE = 6, MAX_RESOURCES = 45;
-
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
 
 uint32_t nof_resources(const pdcch_alloc& a)
 {

@@ -184,15 +184,4 @@ std::vector<float> prach_root_sequence(uint32_t L, uint32_t u)
   return y;
 }
 
-std::vector<float> prach_twiddles(uint32_t N)
-{
-  std::vector<float> t(2u * N);
-  for (uint32_t k = 0; k < N; ++k) {
-    const double a = 2.0 * PI * static_cast<double>(k) / static_cast<double>(N);
-    t[2u * k]      = static_cast<float>(std::cos(a));
-    t[2u * k + 1u] = static_cast<float>(std::sin(a));
-  }
-  return t;
-}
-
 } // namespace srsgpu

@@ -78,12 +78,9 @@ void prach_jobs(const srsgpu_prach_occasion& o, const prach_derived& d, const st
 /// evaluated in double in closed form: y_u(n) = x_u*(u^-1 n) y_u(0), y_u(0) the direct sum.
 std::vector<float> prach_root_sequence(uint32_t L, uint32_t u);
 
-/// exp(+j 2 pi k / N), k = 0..N-1, as (re, im) floats.
-std::vector<float> prach_twiddles(uint32_t N);
-
 /// Butterfly j (0..N/4-1) of the radix-4 Stockham pass with sub-transform length ns (1, 4, 16, ...) of an inverse
-/// (exp(+j)) N-point transform: in -> out. tw is prach_twiddles(tw_n), tw_n a multiple of N. The arithmetic is written
-/// out: it compiles for the host too, where signal_device.h's helpers do not exist.
+/// (exp(+j)) N-point transform: in -> out. tw is unit_roots(tw_n) of host_util.h, tw_n a multiple of N. The arithmetic is
+/// written out: it compiles for the host too, where signal_device.h's helpers do not exist.
 SRSGPU_HD void prach_stockham4(const cpx* in, cpx* out, const cpx* tw, uint32_t tw_n, uint32_t N, uint32_t ns,
                                uint32_t j)
 {

@@ -67,12 +67,6 @@ std::vector<float> pucch_f2_dmrs(const srsgpu_pucch_f2_config& c, uint32_t i);
 /// Scrambling bits c(32 w + b) of c_init = rnti 2^15 + n_id as bit b of words[w].
 void pucch_f2_scrambling(const srsgpu_pucch_f2_config& c, uint32_t words[PUCCH_F2_SCR_WORDS]);
 
-/// initialize_symbol_start_epochs in float, 14 or 12 entries.
-std::vector<float> pucch_f2_symbol_epochs(uint32_t numerology, bool cp_extended);
-
-/// exp(+j 2 pi k / 128), k = 0..127, as (re, im) floats.
-std::vector<float> pucch_f2_twiddles();
-
 /// The job of an accepted PDU.
 pucch_f2_job pucch_f2_make_job(const srsgpu_pucch_f2_config& c, uint32_t grid_nof_prb, uint32_t grid_nof_ports,
                                const uint32_t dmrs_rows[2], uint32_t scramble_word);

@@ -1,35 +1,13 @@
 // Derived quantities, refusals, sequences and job descriptors of the PUCCH Format 3 / 4 plan; see pucch_f34_host.h.
 #include "pucch_f34_host.h"
+#include "host_util.h"
 #include "low_papr_host.h"
-#include "pucch_f2_host.h"
-#include "pucch_host.h"
-#include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 namespace srsgpu {
 
 namespace {
-
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
-
-constexpr double PI = 3.14159265358979323846;
-
-uint32_t crc_size(uint32_t a)
-{
-  return a < 12 ? 0 : a < 20 ? 6 : 11;
-}
 
 bool hopping(const srsgpu_pucch_f34_config& c)
 {
@@ -115,10 +93,10 @@ float pucch_f34_code_rate(const srsgpu_pucch_f34_config& c)
   const uint32_t n_data = nof_data_symbols(c);
   const uint32_t per_re = c.pi2_bpsk ? 12u : 24u;
   const uint32_t e_uci  = c.format == 4 ? per_re * n_data / c.occ_length : per_re * n_data * c.nof_prb;
-  const uint32_t ncb    = ((c.nof_uci_bits >= 360 && e_uci >= 1088) || c.nof_uci_bits >= 1013) ? 2u : 1u;
+  const uint32_t ncb    = uci_nof_codeblocks(c.nof_uci_bits, e_uci);
   // pucch_info.h:116: the Format 4 channel bits are 12 n_data Qm, not divided by the spreading factor.
   const uint32_t channel_bits = (c.format == 4 ? 1u : c.nof_prb) * 12u * n_data * (c.pi2_bpsk ? 1u : 2u);
-  return static_cast<float>(c.nof_uci_bits + ncb * crc_size(c.nof_uci_bits)) / static_cast<float>(channel_bits);
+  return static_cast<float>(c.nof_uci_bits + ncb * uci_crc_size(c.nof_uci_bits)) / static_cast<float>(channel_bits);
 }
 
 std::string pucch_f34_refusal(const srsgpu_pucch_f34_config& c, uint32_t grid_nof_prb, uint32_t grid_nof_ports,
@@ -127,14 +105,8 @@ std::string pucch_f34_refusal(const srsgpu_pucch_f34_config& c, uint32_t grid_no
   if (c.format != 3 && c.format != 4) {
     return format("format %u is neither 3 nor 4", c.format);
   }
-  if (c.numerology > 4) {
-    return format("numerology %u is outside 0..4", c.numerology);
-  }
-  if (c.cp_extended > 1 || (c.cp_extended == 1 && c.numerology != 2)) {
-    return format("the extended cyclic prefix exists at numerology 2 only (numerology %u)", c.numerology);
-  }
-  if (c.slot_index >= (10u << c.numerology)) {
-    return format("slot index %u is outside the frame of %u slots", c.slot_index, 10u << c.numerology);
+  if (std::string why = slot_refusal(c.numerology, c.cp_extended, c.slot_index); !why.empty()) {
+    return why;
   }
   if (c.additional_dmrs > 1 || c.pi2_bpsk > 1) {
     return format("additional_dmrs %u and pi2_bpsk %u are flags (0 or 1)", c.additional_dmrs, c.pi2_bpsk);
@@ -170,27 +142,11 @@ std::string pucch_f34_refusal(const srsgpu_pucch_f34_config& c, uint32_t grid_no
     return format("PUCCH Format %u: PRB allocation outside grid (second hop). Requested [%u, %u), grid has %u PRBs.",
                   c.format, c.second_hop_prb, c.second_hop_prb + c.nof_prb, grid_nof_prb);
   }
-  const uint32_t nsymb = pucch_nsymb_per_slot(c.cp_extended);
-  if (c.start_symbol_index + c.nof_symbols > nsymb) {
-    return format("OFDM symbol allocation goes up to symbol %u, exceeding the number of symbols in the given slot with "
-                  "%s CP, i.e., %u.", c.start_symbol_index + c.nof_symbols, c.cp_extended ? "extended" : "normal", nsymb);
+  if (std::string why = symbol_allocation_refusal(c.start_symbol_index, c.nof_symbols, c.cp_extended); !why.empty()) {
+    return why;
   }
-  if (c.nof_ports == 0) {
-    return "The number of receive ports cannot be zero.";
-  }
-  if (c.nof_ports > grid_nof_ports || c.nof_ports > PUCCH_F34_MAX_PORTS) {
-    return format("The number of receive ports, i.e. %u, exceeds the configured maximum number of receive ports, i.e., %u.",
-                  c.nof_ports, std::min(grid_nof_ports, PUCCH_F34_MAX_PORTS));
-  }
-  for (uint32_t r = 0; r < c.nof_ports; ++r) {
-    if (c.ports[r] >= grid_nof_ports) {
-      return format("Rx port %u lies outside the grid (%u ports)", c.ports[r], grid_nof_ports);
-    }
-    for (uint32_t q = 0; q < r; ++q) {
-      if (c.ports[q] == c.ports[r]) {
-        return format("Rx port %u is listed twice", c.ports[r]);
-      }
-    }
+  if (std::string why = rx_ports_refusal(c.ports, c.nof_ports, grid_nof_ports, PUCCH_F34_MAX_PORTS); !why.empty()) {
+    return why;
   }
   // The validators check the code rate before the payload size (pucch_processor_impl.cpp:677 / :686, :764 / :773).
   const float rate = pucch_f34_code_rate(c);
@@ -203,34 +159,20 @@ std::string pucch_f34_refusal(const srsgpu_pucch_f34_config& c, uint32_t grid_no
   if (c.n_id_scrambling > 1023 || c.n_id_hopping > 1023) {
     return format("n_id_scrambling %u or n_id_hopping %u is outside 0..1023", c.n_id_scrambling, c.n_id_hopping);
   }
-  if (c.grid_index >= nof_grids) {
-    return format("grid_index %u is outside the %u grids", c.grid_index, nof_grids);
+  if (std::string why = grid_index_refusal(c.grid_index, nof_grids); !why.empty()) {
+    return why;
   }
-  if (c.llr_offset % 4u != 0) {
-    return format("llr_offset %u is no multiple of 4", c.llr_offset);
-  }
-  if (static_cast<uint64_t>(c.llr_offset) + pucch_f34_nof_llrs(c) > 0xffffffffull) {
-    return format("llr_offset %u leaves no room for the LLRs below 2^32", c.llr_offset);
-  }
-  return {};
+  return llr_offset_refusal(c.llr_offset, pucch_f34_nof_llrs(c));
 }
 
 std::string pucch_f34_llr_overlap(const srsgpu_pucch_f34_config* cfgs, uint32_t nof_pdus)
 {
-  std::vector<std::pair<uint64_t, uint32_t>> order;  // (offset, PDU)
-  order.reserve(nof_pdus);
+  std::vector<uint32_t> offsets(nof_pdus), lengths(nof_pdus);
   for (uint32_t i = 0; i < nof_pdus; ++i) {
-    order.emplace_back(cfgs[i].llr_offset, i);
+    offsets[i] = cfgs[i].llr_offset;
+    lengths[i] = pucch_f34_nof_llrs(cfgs[i]);
   }
-  std::sort(order.begin(), order.end());
-  for (uint32_t k = 1; k < nof_pdus; ++k) {
-    const srsgpu_pucch_f34_config& a = cfgs[order[k - 1].second];
-    if (order[k - 1].first + pucch_f34_nof_llrs(a) > order[k].first) {
-      return format("the LLRs of PDU %u (%u at offset %u) overlap those of PDU %u (offset %u)", order[k - 1].second,
-                    pucch_f34_nof_llrs(a), a.llr_offset, order[k].second, cfgs[order[k].second].llr_offset);
-    }
-  }
-  return {};
+  return llr_overlap(offsets.data(), lengths.data(), nof_pdus);
 }
 
 std::vector<float> pucch_f34_dmrs(const srsgpu_pucch_f34_config& c, uint32_t symbol)
@@ -238,39 +180,13 @@ std::vector<float> pucch_f34_dmrs(const srsgpu_pucch_f34_config& c, uint32_t sym
   static const uint32_t m0_of_occ[4] = {0, 6, 3, 9};  // TS 38.211 Table 6.4.1.3.3.1-1
   const uint32_t        m0    = c.format == 4 ? m0_of_occ[c.occ_index & 3u] : 0u;
   const uint32_t        alpha = (m0 + pucch_n_cs(c.n_id_hopping, pucch_nsymb_per_slot(c.cp_extended), c.slot_index, symbol)) % 12u;
-  const uint32_t        m     = 12u * c.nof_prb;
-  std::vector<int>      arg;
-  unsigned              nzc = 4;
-  std::vector<float>    out;
-  if (!low_papr_argument(c.n_id_hopping % 30u, m, arg, nzc)) {
-    return out;
-  }
-  out.resize(2 * m);
-  for (uint32_t n = 0; n < m; ++n) {
-    const double a = PI * static_cast<double>(arg[n]) / static_cast<double>(nzc) +
-                     2.0 * PI * static_cast<double>((alpha * n) % 12u) / 12.0;
-    out[2 * n]     = static_cast<float>(std::cos(a));
-    out[2 * n + 1] = static_cast<float>(std::sin(a));
-  }
-  return out;
+  // alpha 12ths of a turn per element are 2 alpha 24ths.
+  return low_papr_shifted_sequence(c.n_id_hopping % 30u, 12u * c.nof_prb, 2u * alpha);
 }
 
 std::vector<uint32_t> pucch_f34_scrambling(const srsgpu_pucch_f34_config& c, uint32_t nof_bits)
 {
-  // The Gold sequence of TS 38.211 section 5.2.1 (N_C = 1600), bit i of x1 / x2 holding x(n + i).
-  const uint32_t        c_init = static_cast<uint32_t>(c.rnti) * (1u << 15) + c.n_id_scrambling;
-  std::vector<uint32_t> words((nof_bits + 31u) / 32u, 0u);
-  uint32_t              x1 = 1, x2 = c_init & 0x7fffffffu;
-  for (uint32_t n = 0, end = 1600 + 32u * static_cast<uint32_t>(words.size()); n < end; ++n) {
-    if (n >= 1600) {
-      words[(n - 1600) >> 5] |= ((x1 ^ x2) & 1u) << ((n - 1600) & 31u);
-    }
-    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
-    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
-    x1                = (x1 >> 1) | (f1 << 30);
-    x2                = (x2 >> 1) | (f2 << 30);
-  }
-  return words;
+  return gold_words(static_cast<uint32_t>(c.rnti) * (1u << 15) + c.n_id_scrambling, (nof_bits + 31u) / 32u);
 }
 
 std::vector<float> pucch_f4_w(uint32_t occ_length, uint32_t occ_index)
@@ -294,25 +210,15 @@ std::vector<float> pucch_f4_w(uint32_t occ_length, uint32_t occ_index)
   return out;
 }
 
-std::vector<float> pucch_f34_roots(uint32_t m)
-{
-  std::vector<float> t(2 * m);
-  for (uint32_t k = 0; k < m; ++k) {
-    const double a = 2.0 * PI * static_cast<double>(k) / static_cast<double>(m);
-    t[2 * k]       = static_cast<float>(std::cos(a));
-    t[2 * k + 1]   = static_cast<float>(std::sin(a));
-  }
-  return t;
-}
-
 pucch_f34_job pucch_f34_make_job(const srsgpu_pucch_f34_config& c, uint32_t grid_nof_prb, uint32_t grid_nof_ports,
                                  uint32_t dmrs_row, uint32_t root_row, uint32_t scramble_word)
 {
   pucch_f34_job j;
   std::memset(&j, 0, sizeof(j));
-  j.nsc           = 12u * grid_nof_prb;
-  j.port_stride   = 14u * j.nsc;
-  j.grid_base     = c.grid_index * grid_nof_ports * j.port_stride;
+  const grid_geometry g(grid_nof_prb, grid_nof_ports, c.grid_index);
+  j.nsc           = g.nsc;
+  j.port_stride   = g.port_stride;
+  j.grid_base     = g.grid_base;
   j.llr_offset    = c.llr_offset;
   j.nof_llrs      = pucch_f34_nof_llrs(c);
   j.format        = c.format;
@@ -345,7 +251,7 @@ pucch_f34_job pucch_f34_make_job(const srsgpu_pucch_f34_config& c, uint32_t grid
       j.data_symbol[j.nof_data++] = static_cast<uint8_t>(c.start_symbol_index + i);
     }
   }
-  const std::vector<float> ep = pucch_f2_symbol_epochs(c.numerology, c.cp_extended != 0);
+  const std::vector<float> ep = symbol_epochs(c.numerology, c.cp_extended != 0);
   for (uint32_t hop = 0; hop < 2; ++hop) {
     j.cfo_delta[hop] = 1.0F;
     if (j.hop_nof_dmrs[hop] >= 2) {

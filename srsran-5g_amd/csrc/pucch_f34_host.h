@@ -83,9 +83,6 @@ std::vector<uint32_t> pucch_f34_scrambling(const srsgpu_pucch_f34_config& c, uin
 /// TS 38.211 Tables 6.3.2.6.3-1 / -2: w_n(k), k = 0..11, as (re, im) floats; empty for another length or index.
 std::vector<float> pucch_f4_w(uint32_t occ_length, uint32_t occ_index);
 
-/// exp(+j 2 pi k / m), k = 0..m-1, as (re, im) floats evaluated in double.
-std::vector<float> pucch_f34_roots(uint32_t m);
-
 /// The job of an accepted PDU.
 pucch_f34_job pucch_f34_make_job(const srsgpu_pucch_f34_config& c, uint32_t grid_nof_prb, uint32_t grid_nof_ports,
                                  uint32_t dmrs_row, uint32_t root_row, uint32_t scramble_word);

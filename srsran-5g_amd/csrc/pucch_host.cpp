@@ -1,41 +1,14 @@
 // Refusals, cyclic shift hopping, tables and job descriptors of the PUCCH detector plan; see pucch_host.h.
 #include "pucch_host.h"
+#include "host_util.h"
 #include "low_papr_tables.h"
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 namespace srsgpu {
 
 namespace {
-
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
-
-/// Bits c(8 b) .. c(8 b + 7) of the Gold sequence (TS 38.211 section 5.2.1, N_C = 1600) with initial state c_init.
-void gold_byte_bits(uint32_t c_init, uint32_t b, uint8_t bits[8])
-{
-  uint32_t x1 = 1, x2 = c_init & 0x7fffffffu;  // bit i: x(n + i)
-  for (uint32_t n = 0, end = 1600 + 8 * b + 8; n < end; ++n) {
-    if (n >= 1600 + 8 * b) {
-      bits[n - 1600 - 8 * b] = static_cast<uint8_t>((x1 ^ x2) & 1u);
-    }
-    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
-    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
-    x1 = (x1 >> 1) | (f1 << 30);
-    x2 = (x2 >> 1) | (f2 << 30);
-  }
-}
 
 /// Slot, CP, symbols, PRBs, n_id and grid shared by both formats' refusals.
 std::string common_refusal(uint32_t slot_index, uint32_t numerology, uint32_t cp_extended, uint32_t starting_prb,
@@ -49,10 +22,8 @@ std::string common_refusal(uint32_t slot_index, uint32_t numerology, uint32_t cp
   if (slot_index >= (10u << numerology)) {
     return format("slot_index %u is outside the %u slots of a frame", slot_index, 10u << numerology);
   }
-  const uint32_t nsymb = pucch_nsymb_per_slot(cp_extended);
-  if (start_symbol + nof_symbols > nsymb) {
-    return format("OFDM symbol allocation goes up to symbol %u, exceeding the number of symbols in the given slot with "
-                  "%s CP, i.e., %u.", start_symbol + nof_symbols, cp_extended != 0 ? "extended" : "normal", nsymb);
+  if (std::string why = symbol_allocation_refusal(start_symbol, nof_symbols, cp_extended); !why.empty()) {
+    return why;
   }
   if (n_id > 1023) {
     return format("The sequence hopping identifier (i.e., %u) is out of the range [0..1024).", n_id);
@@ -63,22 +34,20 @@ std::string common_refusal(uint32_t slot_index, uint32_t numerology, uint32_t cp
   if (second_hop_prb != PUCCH_NO_HOP && second_hop_prb >= grid_nof_prb) {
     return format("Second hop PRB %u lies outside the grid (%u PRBs)", second_hop_prb, grid_nof_prb);
   }
-  if (grid_index >= nof_grids) {
-    return format("grid_index %u is outside the %u grids", grid_index, nof_grids);
-  }
-  return {};
+  return grid_index_refusal(grid_index, nof_grids);
 }
 
 void fill_common(pucch_job& j, uint32_t slot_index, uint32_t cp_extended, uint32_t starting_prb, uint32_t second_hop_prb,
                  uint32_t second_hop_first, uint32_t start_symbol, uint32_t nof_symbols, uint32_t n_id, uint32_t m0,
                  uint32_t grid_index, uint32_t grid_nof_prb, uint32_t grid_nof_ports)
 {
-  const uint32_t nsc = 12 * grid_nof_prb, port_stride = 14 * nsc, nsymb = pucch_nsymb_per_slot(cp_extended);
-  j.port_stride  = port_stride;
+  const grid_geometry g(grid_nof_prb, grid_nof_ports, grid_index);
+  const uint32_t      nsymb = pucch_nsymb_per_slot(cp_extended);
+  j.port_stride  = g.port_stride;
   j.nof_symbols  = static_cast<uint8_t>(nof_symbols);
   for (uint32_t i = 0; i < nof_symbols; ++i) {
     const uint32_t prb = (second_hop_prb != PUCCH_NO_HOP && i >= second_hop_first) ? second_hop_prb : starting_prb;
-    j.sym_base[i]      = grid_index * grid_nof_ports * port_stride + (start_symbol + i) * nsc + 12 * prb;
+    j.sym_base[i]      = g.grid_base + (start_symbol + i) * g.nsc + 12 * prb;
     j.alpha[i]         = static_cast<uint8_t>((m0 + pucch_n_cs(n_id, nsymb, slot_index, start_symbol + i)) % 12);
   }
   // compute_group_sequence with neither group nor sequence hopping: u = n_id mod 30, v = 0.
@@ -89,17 +58,6 @@ void fill_common(pucch_job& j, uint32_t slot_index, uint32_t cp_extended, uint32
 }
 
 } // namespace
-
-uint32_t pucch_n_cs(uint32_t n_id, uint32_t nsymb_per_slot, uint32_t n_slot, uint32_t symbol)
-{
-  uint8_t bits[8];
-  gold_byte_bits(n_id, nsymb_per_slot * n_slot + symbol, bits);
-  uint32_t v = 0;
-  for (uint32_t m = 0; m < 8; ++m) {
-    v |= static_cast<uint32_t>(bits[m]) << m;
-  }
-  return v;
-}
 
 float pucch_f0_threshold(uint32_t nof_ports, uint32_t nof_symbols, uint32_t nof_sequences)
 {

@@ -1,6 +1,6 @@
 // Host-side construction for the PUCCH Format 0 / 1 detector plan (capi_pucch.cpp, pucch_detector.hip): the refusals,
-// the cyclic shift hopping n_cs, the Format 0 candidate tables and thresholds, the Format 1 hop split and thresholds,
-// and the orthogonal sequences. No HIP call in this translation unit, so that a host-only program can check it
+// the Format 0 candidate tables and thresholds, the Format 1 hop split and thresholds, and the orthogonal sequences;
+// the cyclic shift hopping n_cs (pucch_n_cs) is in host_util.h. No HIP call in this translation unit, so that a host-only program can check it
 // (tools/pucch_host_check.cpp).
 //
 // Reference (behaviour, not code): include/srsran/phy/upper/pucch_helper.h:52 (u, v) / :81 (alpha index),
@@ -40,13 +40,6 @@ struct pucch_job {
   uint8_t  occ_mask;       ///< Format 1: bit i set = an entry has OCC i.
   uint8_t  reserved;
 };
-
-/// Symbols of a slot: 14, or 12 with the extended CP.
-inline uint32_t pucch_nsymb_per_slot(uint32_t cp_extended) { return cp_extended != 0 ? 12 : 14; }
-
-/// n_cs(n_slot, symbol) of TS 38.211 section 6.3.2.2.2 with c_init = n_id: the byte nsymb n_slot + symbol of the Gold
-/// sequence, its first bit the least significant (pucch_helper.h:105: get_byte, then reverse_byte).
-uint32_t pucch_n_cs(uint32_t n_id, uint32_t nsymb_per_slot, uint32_t n_slot, uint32_t symbol);
 
 /// pick_threshold (pucch_detector_format0.cpp:69): std::lower_bound over (ports x symbols, sequences) pairs in
 /// lexicographic order, so 3 ports x 1 symbol takes the (4, 1) entry whatever the number of sequences. 0 past the table.

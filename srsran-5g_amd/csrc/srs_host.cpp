@@ -1,28 +1,15 @@
 // Derived quantities, refusals, sequences and job descriptors of the SRS estimator plan; see srs_host.h.
 #include "srs_host.h"
+#include "host_util.h"
 #include "low_papr_host.h"
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 namespace srsgpu {
 
 namespace {
 
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
-
-constexpr double PI  = 3.14159265358979323846;
 constexpr double T_C = 1.0 / (480000.0 * 4096.0);  // phy_time_unit::T_C
 
 } // namespace
@@ -31,8 +18,8 @@ std::string srs_refusal(const srsgpu_srs_config& c, uint32_t grid_nof_prb, uint3
                         uint32_t nof_resources, srs_derived& d)
 {
   std::memset(&d, 0, sizeof(d));
-  if (c.numerology > 4) {
-    return format("numerology %u is outside 0..4", c.numerology);
+  if (std::string why = numerology_refusal(c.numerology); !why.empty()) {
+    return why;
   }
   if (c.nof_antenna_ports != 1 && c.nof_antenna_ports != 2 && c.nof_antenna_ports != 4) {
     return format("The number of antenna ports (i.e., %u) is not 1, 2 or 4.", c.nof_antenna_ports);
@@ -66,15 +53,8 @@ std::string srs_refusal(const srsgpu_srs_config& c, uint32_t grid_nof_prb, uint3
   if (c.nof_rx_ports > SRS_MAX_PORTS) {
     return format("The number of receive ports (i.e., %u) exceeds 4", c.nof_rx_ports);
   }
-  for (uint32_t r = 0; r < c.nof_rx_ports; ++r) {
-    if (c.rx_ports[r] >= grid_nof_ports) {
-      return format("Rx port %u lies outside the grid (%u ports)", c.rx_ports[r], grid_nof_ports);
-    }
-    for (uint32_t q = 0; q < r; ++q) {
-      if (c.rx_ports[q] == c.rx_ports[r]) {
-        return format("Rx port %u is listed twice", c.rx_ports[r]);
-      }
-    }
+  if (std::string why = rx_port_list_refusal(c.rx_ports, c.nof_rx_ports, grid_nof_ports); !why.empty()) {
+    return why;
   }
   if (c.start_symbol + c.nof_symbols > 14u) {
     return format("The start symbol index (i.e., %u) plus the number of symbols (i.e., %u) exceeds the number of symbols "
@@ -93,8 +73,8 @@ std::string srs_refusal(const srsgpu_srs_config& c, uint32_t grid_nof_prb, uint3
       return format("Table row: m_srs[%u] x N[%u] = %u x %u does not give the bandwidth above it", b, b, c.m_srs[b], c.N[b]);
     }
   }
-  if (c.grid_index >= nof_grids) {
-    return format("grid_index %u is outside the %u grids", c.grid_index, nof_grids);
+  if (std::string why = grid_index_refusal(c.grid_index, nof_grids); !why.empty()) {
+    return why;
   }
   if (c.result_index >= nof_resources) {
     return format("result_index %u is outside the %u resources", c.result_index, nof_resources);
@@ -145,9 +125,10 @@ srs_job srs_make_job(const srsgpu_srs_config& c, const srs_derived& d, const uin
 {
   srs_job j;
   std::memset(&j, 0, sizeof(j));
-  j.nsc            = 12u * grid_nof_prb;
-  j.port_stride    = 14u * j.nsc;
-  j.grid_base      = c.grid_index * grid_nof_ports * j.port_stride;
+  const grid_geometry g(grid_nof_prb, grid_nof_ports, c.grid_index);
+  j.nsc            = g.nsc;
+  j.port_stride    = g.port_stride;
+  j.grid_base      = g.grid_base;
   j.result_index   = c.result_index;
   j.L              = d.L;
   j.comb           = c.comb_size;
@@ -171,32 +152,10 @@ srs_job srs_make_job(const srsgpu_srs_config& c, const srs_derived& d, const uin
 
 std::vector<float> srs_sequence(uint32_t u, uint32_t L, uint32_t n_cs, uint32_t n_cs_max)
 {
-  std::vector<int>   arg;
-  unsigned           nzc = 4;
-  std::vector<float> out;
-  if (u >= 30 || n_cs_max == 0 || !low_papr_argument(u, L, arg, nzc)) {
-    return out;
+  if (u >= 30 || n_cs_max == 0) {
+    return {};
   }
-  const uint64_t step = static_cast<uint64_t>(n_cs) * 24u / n_cs_max;  // generate(): alpha_num x 24 / alpha_den
-  out.reserve(2 * static_cast<size_t>(L));
-  for (uint32_t n = 0; n < L; ++n) {
-    const double a = PI * static_cast<double>(arg[n]) / static_cast<double>(nzc) +
-                     2.0 * PI * static_cast<double>((n * step) % 24u) / 24.0;
-    out.push_back(static_cast<float>(std::cos(a)));
-    out.push_back(static_cast<float>(std::sin(a)));
-  }
-  return out;
-}
-
-std::vector<float> srs_cexp_table()
-{
-  std::vector<float> t(2 * SRS_CEXP_SIZE);
-  for (uint32_t k = 0; k < SRS_CEXP_SIZE; ++k) {
-    const double a = 2.0 * PI * static_cast<double>(k) / static_cast<double>(SRS_CEXP_SIZE);
-    t[2 * k]       = static_cast<float>(std::cos(a));
-    t[2 * k + 1]   = static_cast<float>(std::sin(a));
-  }
-  return t;
+  return low_papr_shifted_sequence(u, L, static_cast<uint64_t>(n_cs) * 24u / n_cs_max);  // generate(): alpha_num x 24 / alpha_den
 }
 
 } // namespace srsgpu

@@ -64,7 +64,4 @@ srs_job srs_make_job(const srsgpu_srs_config& c, const srs_derived& d, const uin
 /// Empty for a length the specification does not define.
 std::vector<float> srs_sequence(uint32_t u, uint32_t L, uint32_t n_cs, uint32_t n_cs_max);
 
-/// exp(+j 2 pi k / 1024), k = 0..1023, as (re, im) floats.
-std::vector<float> srs_cexp_table();
-
 } // namespace srsgpu

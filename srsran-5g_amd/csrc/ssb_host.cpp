@@ -1,24 +1,11 @@
 // Refusals, positions, payload layout and sequences of the SS/PBCH block plan; see ssb_host.h.
 #include "ssb_host.h"
+#include "host_util.h"
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <vector>
 
 namespace srsgpu {
 
 namespace {
-
-std::string format(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string format(const char* fmt, ...)
-{
-  char    buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return buf;
-}
 
 /// TS 38.212 Table 7.1.1-1: the PBCH payload interleaver pattern G(j).
 constexpr uint8_t G[32] = {16, 23, 18, 17, 8, 30, 10, 6, 24, 7, 0, 5, 3, 2, 1, 4,
@@ -156,24 +143,6 @@ std::string ssb_refusal(const ssb_block& b, uint32_t grid_nof_prb, uint32_t grid
   return {};
 }
 
-void ssb_gold_bits(uint32_t c_init, uint32_t first, uint32_t count, uint8_t* out)
-{
-  constexpr uint32_t   NC = 1600;
-  const uint32_t       n  = NC + first + count;
-  std::vector<uint8_t> x1(n + 31, 0), x2(n + 31, 0);
-  x1[0] = 1;
-  for (uint32_t i = 0; i < 31; ++i) {
-    x2[i] = (c_init >> i) & 1u;
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    x1[i + 31] = x1[i + 3] ^ x1[i];
-    x2[i + 31] = x2[i + 3] ^ x2[i + 2] ^ x2[i + 1] ^ x2[i];
-  }
-  for (uint32_t i = 0; i < count; ++i) {
-    out[i] = x1[NC + first + i] ^ x2[NC + first + i];
-  }
-}
-
 void ssb_fill_tables(ssb_tables& t)
 {
   // The payload's bits 1..6 (the SFN's MSBs) go to G(0..5), the others to G(14..31); then the SFN's four LSBs.
@@ -215,7 +184,7 @@ void ssb_fill_desc(const ssb_block& b, ssb_desc& d)
   // The scrambling sequence of N_id from M v on, M the number of scrambled positions, spread over those positions.
   const uint32_t M = l64 ? 26 : 29;
   uint8_t        c[4 * 29];
-  ssb_gold_bits(b.phys_cell_id, 0, 4 * M, c);
+  gold_bits(b.phys_cell_id, 0, 4 * M, c);
   for (uint32_t v = 0; v < 4; ++v) {
     uint32_t mask = 0, j = 0;
     for (uint32_t i = 0; i < 32; ++i) {

@@ -78,7 +78,4 @@ void ssb_fill_desc(const ssb_block& b, ssb_desc& d);
 /// dyn_source, v_hi, v_lo and crc_weights (the code tables come from polar_dl_code_build).
 void ssb_fill_tables(ssb_tables& t);
 
-/// TS 38.211 section 5.2.1: c(first) .. c(first + count - 1) of initial state c_init, one bit per byte.
-void ssb_gold_bits(uint32_t c_init, uint32_t first, uint32_t count, uint8_t* out);
-
 } // namespace srsgpu

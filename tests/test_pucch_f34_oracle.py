@@ -207,7 +207,6 @@ def test_host_code(tmp_path):
     csrc = os.path.join(ROOT, "srsran-5g_amd", "csrc")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     f"-I{csrc}", f"-I{os.path.join(ROOT, 'include')}", "-o", exe, os.path.join(csrc, "pucch_f34_host.cpp"),
-                    os.path.join(csrc, "pucch_f2_host.cpp"), os.path.join(csrc, "pucch_host.cpp"),
                     os.path.join(ROOT, "tools", "pucch_f34_host_check.cpp")], check=True)
     cfgs = [c["cfg"] for c in C.golden()][::4]
     assert len(pack_config(cfgs[0], 0, 0)) == 40

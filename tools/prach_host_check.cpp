@@ -8,6 +8,7 @@
 // Checks prach_derive and prach_window_start against the dump, prach_root_sequence against the dump and against a
 // direct sum, the radix-4 Stockham passes (prach_stockham4, the code the kernel runs) against a direct sum for 1024 and
 // 256 points, the job descriptors and every refusal.
+#include "host_util.h"
 #include "prach_host.h"
 #include <cmath>
 #include <cstdio>
@@ -47,7 +48,7 @@ T take(const std::vector<char>& raw, size_t& pos)
 
 void check_stockham(uint32_t N)
 {
-  const std::vector<float> twf = prach_twiddles(PRACH_LONG_N);
+  const std::vector<float> twf = unit_roots(PRACH_LONG_N);
   std::vector<cpx>         tw(PRACH_LONG_N), a(N), b(N);
   std::memcpy(static_cast<void*>(tw.data()), twf.data(), twf.size() * sizeof(float));
   uint32_t state = 12345u + N;
@@ -198,7 +199,7 @@ int main(int argc, char** argv)
   CHECK(pos == raw.size(), "dump has %zu bytes left", raw.size() - pos);
   check_stockham(PRACH_LONG_N);
   check_stockham(PRACH_SHORT_N);
-  const std::vector<float> tw = prach_twiddles(8);
+  const std::vector<float> tw = unit_roots(8);
   CHECK(tw.size() == 16 && tw[0] == 1.0F && std::fabs(tw[5] - 1.0F) < 1e-7F && std::fabs(tw[8] + 1.0F) < 1e-7F, "twiddles");
   check_refusals();
   std::printf("%u derived rows, %u root sequences, %d failures\n", n, m, failures);

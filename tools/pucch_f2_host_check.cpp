@@ -7,6 +7,7 @@
 //                              11 f32 taps, f32 epoch distance of the two symbols (1 with one symbol)).
 // Checks the DM-RS, the scrambling words, the filter, the epochs and the job descriptors against the dump, the code
 // rate, the twiddles, every refusal and the overlap search.
+#include "host_util.h"
 #include "pucch_f2_host.h"
 #include <cmath>
 #include <cstdio>
@@ -127,15 +128,15 @@ void check_tables()
     }
     CHECK(std::fabs(sum - 1.0F) < 1e-6F && taps[5] > taps[4] && taps[0] == taps[10], "%u PRB: taps sum %g", prb, sum);
   }
-  const std::vector<float> tw = pucch_f2_twiddles();
+  const std::vector<float> tw = unit_roots(PUCCH_F2_DFT);
   CHECK(tw.size() == 256 && tw[0] == 1.0F && tw[1] == 0.0F && std::fabs(tw[2 * 32]) < 1e-7F && tw[2 * 32 + 1] == 1.0F &&
             tw[2 * 64] == -1.0F,
         "twiddles");
   // Normal CP, 30 kHz: symbols 0 and 14 x ... carry 16 kappa more; the distance of two plain symbols is 1 + 72 / 1024.
-  const std::vector<float> ep = pucch_f2_symbol_epochs(1, false);
+  const std::vector<float> ep = symbol_epochs(1, false);
   CHECK(ep.size() == 14 && std::fabs(ep[0] - 88.0F / 1024.0F) < 1e-6F && std::fabs(ep[5] - ep[4] - (1.0F + 72.0F / 1024.0F)) < 1e-5F,
         "epochs %g %g", ep[0], ep[5] - ep[4]);
-  const std::vector<float> ex = pucch_f2_symbol_epochs(2, true);
+  const std::vector<float> ex = symbol_epochs(2, true);
   CHECK(ex.size() == 12 && std::fabs(ex[3] - ex[2] - 1.25F) < 1e-5F, "extended epochs %g", ex[3] - ex[2]);
 }
 

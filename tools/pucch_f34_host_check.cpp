@@ -8,6 +8,7 @@
 //       and the words; 12 x (f32 re, f32 im) of w_n (Format 4 only); 2 x f32 epoch distances of the hops' first two
 //       DM-RS symbols (1 where a hop has one); u32 number of data symbols and per data symbol u8 symbol, u8 hop.
 // Then the hand-made part: the DM-RS table's shape, every refusal with its message, the code rates, the overlap search.
+#include "host_util.h"
 #include "pucch_f34_host.h"
 #include <cmath>
 #include <cstdio>
@@ -218,7 +219,7 @@ void hand_made()
   expect(pucch_f34_llr_overlap(two, 0).empty(), "no PDUs");
 
   // Tables: the roots and the orthogonal sequences.
-  const std::vector<float> r = pucch_f34_roots(12);
+  const std::vector<float> r = unit_roots(12);
   expect(r.size() == 24 && std::fabs(r[0] - 1) < 1e-7F && std::fabs(r[6]) < 1e-7F && std::fabs(r[7] - 1) < 1e-7F, "roots");
   expect(pucch_f4_w(3, 0).empty() && pucch_f4_w(2, 2).empty() && pucch_f4_w(4, 3).size() == 24, "w_n lengths");
   const std::vector<uint32_t> words = pucch_f34_scrambling(c, 4608);

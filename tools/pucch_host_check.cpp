@@ -4,6 +4,7 @@
 // descriptors' bounds and every refusal.
 //
 //   pucch_host_check DUMP    DUMP: u32 n, then n x 5 u32 (n_id, symbols per slot, n_slot, symbol, n_cs).
+#include "host_util.h"
 #include "pucch_host.h"
 #include <cmath>
 #include <cstdio>

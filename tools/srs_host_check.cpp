@@ -7,6 +7,7 @@
 //                          u32 m; m x (u32 u, u32 L, u32 n_cs, u32 n_cs_max, 2 L f64: the sequence as (re, im)).
 // Checks srs_refusal's derived quantities and srs_sequence against the dump, the phase table, the job descriptors and
 // every refusal.
+#include "host_util.h"
 #include "srs_host.h"
 #include <cmath>
 #include <cstdio>
@@ -161,7 +162,7 @@ int main(int argc, char** argv)
     CHECK(worst < 2e-7, "sequence u %u L %u n_cs %u / %u deviates by %g", u, L, n_cs, n_cs_max, worst);
   }
   CHECK(pos == raw.size(), "dump has %zu bytes left", raw.size() - pos);
-  const std::vector<float> t = srs_cexp_table();
+  const std::vector<float> t = unit_roots(SRS_CEXP_SIZE);
   CHECK(t.size() == 2048 && t[0] == 1.0F && t[1] == 0.0F && std::fabs(t[2 * 256 + 1] - 1.0F) < 1e-7F && std::fabs(t[2 * 512] + 1.0F) < 1e-7F &&
             std::fabs(t[2 * 128] - std::sqrt(0.5F)) < 1e-7F,
         "phase table");

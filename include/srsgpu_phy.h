@@ -78,7 +78,11 @@ typedef enum {
   /** 1 (default) / 0: a PUSCH decoder plan whose transport blocks all have one codeblock, every one dematched by the
    *  decoder itself, has the decoder kernel write the transport blocks and their CRC flags and skips the TB-stage
    *  launch (0: always the separate TB stage). */
-  SRSGPU_OPTION_DECODER_TB_FOLD = 6
+  SRSGPU_OPTION_DECODER_TB_FOLD = 6,
+  /** 0 (default) / 1: the PUSCH demodulator's general paths for every transmission: the search for an RE's OFDM
+   *  symbol (0: a closed form where every data symbol carries the same number of REs) and LLR-by-LLR descrambling and
+   *  packing (0: four LLRs at a time where layers x modulation order is a multiple of 4). */
+  SRSGPU_OPTION_DEMOD_GENERAL_PATHS = 7
 } srsgpu_option;
 
 /** Sets option `option` (srsgpu_option) of a context for the plans created afterwards. */
@@ -1272,6 +1276,11 @@ int srsgpu_pusch_demodulator_plan_create(srsgpu_context*                  ctx,
 
 /** Number of codeword LLRs of transmission `tx` (data REs x layers x Qm). */
 uint32_t srsgpu_pusch_demodulator_plan_nof_llrs(const srsgpu_pusch_demodulator_plan* plan, uint32_t tx);
+
+/** 1 when the plan finds the OFDM symbol of transmission `tx`'s REs by the closed form (every symbol with data carries
+ *  the same number of REs, no DM-RS symbol carries data, at most two interior runs of symbols without data), 0 when it
+ *  searches the symbols' cumulative RE counts (every other layout, SRSGPU_OPTION_DEMOD_GENERAL_PATHS, or no such tx). */
+int srsgpu_pusch_demodulator_plan_symbol_closed_form(const srsgpu_pusch_demodulator_plan* plan, uint32_t tx);
 
 /** Demodulates every planned transmission into d_llrs. Asynchronous on `stream`, hipGraph-capturable. */
 int srsgpu_pusch_demodulator_plan_execute(const srsgpu_pusch_demodulator_plan* plan,

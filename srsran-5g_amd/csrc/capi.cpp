@@ -466,6 +466,8 @@ int* context_option(srsgpu_context* ctx, int option)
       return &ctx->opt_encoder_zero_output;
     case SRSGPU_OPTION_DECODER_TB_FOLD:
       return &ctx->opt_decoder_tb_fold;
+    case SRSGPU_OPTION_DEMOD_GENERAL_PATHS:
+      return &ctx->opt_demod_general_paths;
     default:
       return nullptr;
   }

@@ -200,6 +200,7 @@ struct srsgpu_context {
   int opt_encoder_byte_kernel   = 0;
   int opt_encoder_zero_output   = 0;
   int opt_decoder_tb_fold       = 1;
+  int opt_demod_general_paths   = 0;
   std::mutex                           mtx;
 };
 

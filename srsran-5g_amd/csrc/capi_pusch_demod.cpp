@@ -22,6 +22,8 @@ struct srsgpu_pusch_demodulator_plan {
   device_buffer<float>            d_acc;   ///< Statistics accumulators (zero between executes).
   int                   nof_chunks = 0;
   int                   chunk_threads = 256;  ///< Lanes per chunk workgroup (launch_pusch_demodulate).
+  bool                  general = false;      ///< Created under SRSGPU_OPTION_DEMOD_GENERAL_PATHS.
+  std::vector<uint8_t>  closed_form;          ///< Per transmission: demod_desc::sym_magic != 0.
   int                   nof_tp_jobs = 0;
   int                   nof_tx     = 0;
   std::vector<uint32_t> nof_llrs;
@@ -102,6 +104,64 @@ demap_pair_table pair_table(unsigned qm, unsigned k)
   return t;
 }
 
+/// Closed form of an RE's OFDM symbol (demod_desc::sym_magic and the fields after it) where the layout allows it:
+/// every symbol with data carries the same number of REs, none of them is a DM-RS symbol, and the symbols without data
+/// between the first and the last data symbol form at most two runs. Leaves sym_magic = 0 (the search) otherwise.
+void demod_symbol_form(demod_desc& d)
+{
+  d.sym_magic      = 0;
+  d.sym_skip_at[0] = d.sym_skip_at[1] = 255;
+  d.sym_skip[0] = d.sym_skip[1] = 0;
+  std::vector<unsigned> data;  // OFDM symbols with data, ascending
+  for (unsigned l = 0; l < 14; ++l) {
+    const unsigned m = static_cast<unsigned>(d.sym_cum[l + 1]) - d.sym_cum[l];
+    if (m == 0) {
+      continue;
+    }
+    const unsigned first = data.empty() ? m : static_cast<unsigned>(d.sym_cum[data[0] + 1]) - d.sym_cum[data[0]];
+    if (m != first || ((d.dmrs_mask >> l) & 1u) != 0) {
+      return;
+    }
+    data.push_back(l);
+  }
+  if (data.empty()) {
+    return;
+  }
+  const unsigned n    = static_cast<unsigned>(d.sym_cum[data[0] + 1]) - d.sym_cum[data[0]];
+  unsigned       runs = 0;
+  uint8_t        at[2] = {255, 255}, len[2] = {0, 0};
+  for (size_t q = 1; q < data.size(); ++q) {
+    const unsigned gap = data[q] - data[q - 1] - 1;
+    if (gap > 0) {
+      if (runs == 2) {
+        return;
+      }
+      at[runs]  = static_cast<uint8_t>(q);
+      len[runs] = static_cast<uint8_t>(gap);
+      ++runs;
+    }
+  }
+  const uint32_t magic = static_cast<uint32_t>(((1ull << 32) + n - 1) / n);
+  // The form against the table at both ends of every data symbol: the quotient is monotonic in r, and
+  // r * (magic * n - 2^32) < 2^16 * n < 2^32 makes it exact in between.
+  const auto symbol_of = [&](uint32_t r) {
+    const uint32_t q = static_cast<uint32_t>((static_cast<uint64_t>(r) * magic) >> 32);
+    return data[0] + q + (q >= at[0] ? len[0] : 0u) + (q >= at[1] ? len[1] : 0u);
+  };
+  for (unsigned l : data) {
+    if (symbol_of(d.sym_cum[l]) != l || symbol_of(d.sym_cum[l + 1] - 1u) != l) {
+      return;
+    }
+  }
+  d.sym_magic = magic;
+  d.sym_res   = static_cast<uint16_t>(n);
+  d.sym_first = static_cast<uint8_t>(data[0]);
+  for (int i = 0; i < 2; ++i) {
+    d.sym_skip_at[i] = at[i];
+    d.sym_skip[i]    = len[i];
+  }
+}
+
 } // namespace
 
 extern "C" {
@@ -131,6 +191,8 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
     return fail(SRSGPU_ERR_INVALID_ARG, "invalid grid geometry (%u PRB, %u ports)", grid_nof_prb, grid_nof_ports);
   }
   const uint32_t          nsc = 12u * grid_nof_prb;
+  // SRSGPU_OPTION_DEMOD_GENERAL_PATHS: no closed form of the symbol, the LLR-by-LLR kernels (parity tests).
+  const bool                general = ctx->opt_demod_general_paths != 0;
   std::vector<demod_desc>   descs(nof_tx);
   std::vector<mod_chunk>    chunks;
   std::vector<demod_tp_job> tp_jobs;
@@ -237,6 +299,10 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
     d.P               = static_cast<uint8_t>(P);
     d.nd_dmrs         = static_cast<uint8_t>(nd);
     d.eq              = (L >= 3 || c.equalizer == SRSGPU_EQ_MMSE) ? DEMOD_EQ_MMSE : DEMOD_EQ_ZF;
+    d.sym_skip_at[0] = d.sym_skip_at[1] = 255;
+    if (!general) {
+      demod_symbol_form(d);
+    }
     descs[t]          = d;
     nllr[t]           = d.nof_llrs;
     const uint32_t nwords = c.transform_precoding ? 0u : (d.nof_llrs + 31) / 32;  // TP: per-symbol jobs instead
@@ -301,6 +367,10 @@ int srsgpu_pusch_demodulator_plan_create_ex(srsgpu_context*                  ctx
   plan->nof_chunks  = static_cast<int>(chunks.size());
   plan->nof_tp_jobs = static_cast<int>(tp_jobs.size());
   plan->nof_tx      = static_cast<int>(nof_tx);
+  plan->general     = general;
+  for (const demod_desc& d : descs) {
+    plan->closed_form.push_back(d.sym_magic != 0 ? 1 : 0);
+  }
   plan->nof_llrs    = std::move(nllr);
   plan->seq_off     = seq_off;
   const bool work   = !chunks.empty() || !tp_jobs.empty();
@@ -332,6 +402,11 @@ uint32_t srsgpu_pusch_demodulator_plan_nof_llrs(const srsgpu_pusch_demodulator_p
   return (plan == nullptr || tx >= plan->nof_llrs.size()) ? 0u : plan->nof_llrs[tx];
 }
 
+int srsgpu_pusch_demodulator_plan_symbol_closed_form(const srsgpu_pusch_demodulator_plan* plan, uint32_t tx)
+{
+  return (plan == nullptr || tx >= plan->closed_form.size()) ? 0 : plan->closed_form[tx];
+}
+
 int srsgpu_pusch_demodulator_plan_execute(const srsgpu_pusch_demodulator_plan* plan,
                                           const uint32_t*                      d_grids,
                                           const uint32_t*                      d_ch_estimates,
@@ -361,8 +436,8 @@ int srsgpu_pusch_demodulator_plan_execute_ex(const srsgpu_pusch_demodulator_plan
   const hipStream_t s   = static_cast<hipStream_t>(stream);
   float*            acc = d_stats != nullptr ? plan->d_acc.get() : nullptr;
   launch_pusch_demodulate(plan->d_desc.get(), plan->d_chunks.get(), plan->nof_chunks, plan->chunk_threads,
-                          plan->d_tables.get(), d_grids, d_ch_estimates, d_noise_var, d_llrs, plan->d_seq.get(),
-                          plan->d_crbs.get(), acc, s);
+                          plan->general, plan->d_tables.get(), d_grids, d_ch_estimates, d_noise_var, d_llrs,
+                          plan->d_seq.get(), plan->d_crbs.get(), acc, s);
   launch_pusch_demodulate_tp(plan->d_desc.get(), plan->d_tp_jobs.get(), plan->nof_tp_jobs, plan->d_tables.get(), d_grids,
                              d_ch_estimates, d_noise_var, d_llrs, plan->d_seq.get(), plan->d_crbs.get(), acc, s);
   if (d_stats != nullptr) {

@@ -546,7 +546,6 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
   const int      K   = G::K;
   const int      nkb = K * Z / 8;  // message bytes
   const int      tid = static_cast<int>(threadIdx.x);
-  const uint8_t* tb  = tbs + d.tb_byte_offset;
   const int      nd8 = d.nof_data / 8;
   // Every global load that depends only on the descriptor is issued up front (edge table, message bytes, the CB CRC's
   // chunk power, the TB CRC word), so their latencies overlap instead of adding up.
@@ -557,17 +556,21 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
     const int e = tid + r * PK_THREADS < G::NE ? tid + r * PK_THREADS : G::NE - 1;
     ev[r]       = (static_cast<uint32_t>(G::col(e)) << 16) | shift_table[static_cast<uint32_t>(d.zpos) * G::NE + e];
   }
-  // All of a lane's message bytes are loaded before any is stored (the address is clamped into the TB so the loads
-  // are unconditional).
-  constexpr int  MB    = (G::K * 384 / 8 + PK_THREADS - 1) / PK_THREADS;
-  const uint32_t tb_hi = d.tb_bits >= 8u ? (d.tb_bits - 8u) >> 3 : 0u;
-  uint32_t       byte[MB];
+  // The codeblock's span of the TB, message bytes [0, ntb), as the aligned 32-bit words that hold at least one of its
+  // bytes (none lies wholly outside the TB), all of a lane's words loaded before any is stored. Message word q is
+  // bytes sh .. sh + 3 of the aligned words q and q + 1.
+  constexpr int   MW   = (G::K * 384 / 32 + PK_THREADS - 1) / PK_THREADS;
+  const int       ntb  = min(nd8, static_cast<int>(d.tb_bits - min(d.tb_bit_offset, d.tb_bits)) / 8);
+  const uint32_t  soff = d.tb_byte_offset + (d.tb_bit_offset >> 3);
+  const uint32_t  sh   = (static_cast<uint32_t>(reinterpret_cast<uintptr_t>(tbs)) + soff) & 3u;
+  const uint8_t*  srcw = tbs + (static_cast<int64_t>(soff) - static_cast<int64_t>(sh));  // 4-byte aligned
+  const int       nsw  = ntb > 0 ? (ntb + static_cast<int>(sh) + 3) / 4 : 0;
+  uint32_t        wlo[MW], whi[MW];
 #pragma unroll
-  for (int r = 0; r < MB; ++r) {
-    const int      q  = tid + r * PK_THREADS;
-    const uint32_t p  = d.tb_bit_offset + 8u * static_cast<uint32_t>(q);
-    const uint32_t pb = p >> 3;
-    byte[r]           = (q < nd8) ? tb[pb < tb_hi ? pb : tb_hi] : 0u;
+  for (int r = 0; r < MW; ++r) {
+    const int q = tid + r * PK_THREADS;
+    wlo[r]      = (q < nsw) ? *reinterpret_cast<const uint32_t*>(srcw + 4 * q) : 0u;
+    whi[r]      = (sh != 0u && q + 1 < nsw) ? *reinterpret_cast<const uint32_t*>(srcw + 4 * q + 4) : 0u;
   }
   constexpr int CB_CS    = 8;
   const bool    has_cbc  = d.crc_table != NO_CRC_TABLE;
@@ -638,18 +641,19 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
   for (int m = tid; m <= G::M; m += PK_THREADS) {
     row_start[m] = static_cast<uint16_t>(G::rs(m));
   }
-  // ---- Message bytes (ldpc_segmenter_tx_impl.cpp:144): TB(+TB CRC) bytes, zero padding / CRC slot / fillers. A
-  // carrier's TB CRC bytes are zero here (tb_crc is) and written once the CRC is known. ----
+  // ---- Message words (ldpc_segmenter_tx_impl.cpp:144): the TB's bytes; the bytes after them (TB CRC, zero padding,
+  // CRC slot, fillers) masked to zero in the boundary word, zero words beyond. The TB CRC's bytes are written below,
+  // a carrier's once its CRC is known. ----
+  {
+    uint32_t* msgw = reinterpret_cast<uint32_t*>(msg);
 #pragma unroll
-  for (int r = 0; r < MB; ++r) {
-    const int q = tid + r * PK_THREADS;
-    if (q < nkb) {
-      const uint32_t p = d.tb_bit_offset + 8u * static_cast<uint32_t>(q);
-      uint32_t       b = byte[r];
-      if (q < nd8 && p >= d.tb_bits) {
-        b = (tb_crc >> (d.tb_crc_len - 8u - (p - d.tb_bits))) & 0xffu;
+    for (int r = 0; r < MW; ++r) {
+      const int q = tid + r * PK_THREADS;
+      if (q < nkb / 4) {
+        const int      nb   = ntb - 4 * q;  // TB bytes from the word's first byte on
+        const uint32_t keep = nb >= 4 ? 0xffffffffu : (nb <= 0 ? 0u : (1u << (8 * nb)) - 1u);
+        msgw[q]             = __builtin_amdgcn_alignbyte(whi[r], wlo[r], sh) & keep;
       }
-      msg[q] = static_cast<uint8_t>(b);
     }
   }
   __syncthreads();  // msg, t4b and t4t complete
@@ -690,7 +694,8 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
                                   crc_tables + tcd.table, static_cast<int>(tcd.order), t4t, red);
   }
   ENC_STAMP(1);
-  if (carrier) {  // the TB CRC's bytes: message bytes [qc, nd8), at most three
+  const bool crc_here = ntb < nd8;  // the codeblock holds bytes of the TB CRC
+  if (crc_here) {  // the TB CRC's bytes: message bytes [qc, nd8), at most three
     const int qc = static_cast<int>(d.tb_bits - min(d.tb_bit_offset, d.tb_bits)) / 8;
     if (tid < nd8 - qc) {
       const uint32_t p = d.tb_bit_offset + 8u * static_cast<uint32_t>(qc + tid);
@@ -699,7 +704,7 @@ __global__ __launch_bounds__(PK_THREADS) void pdsch_encode_packed_kernel(const e
   }
   ENC_STAMP(2);
   if (has_cbc) {
-    if (carrier) {
+    if (crc_here) {
       __syncthreads();  // the TB CRC's bytes in msg
     }
     const uint32_t crc = block_crc_slice4<CB_CS>([](int q) { return msg[q]; }, cb_bytes, crc_tables + d.crc_table, 24,

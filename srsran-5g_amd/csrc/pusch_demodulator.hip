@@ -58,20 +58,42 @@ __device__ __forceinline__ int quantize(float v, float scale)
   return static_cast<int>(__builtin_rintf(x));  // NaN cannot occur: rcp = 0 for invalid noise
 }
 
+/// The same LLR as the low byte of the returned word: adding 1.5 x 2^23 rounds the clipped value half to even into the
+/// low mantissa bits (two's complement), in place of the rounding and the conversion.
+__device__ __forceinline__ uint32_t quantize_byte(float v, float scale)
+{
+  float x = v * scale;
+  x       = fminf(fmaxf(x, -120.f), 120.f);
+  return __float_as_uint(x + 12582912.f);
+}
+
+/// quantize as an int, or, RAW, quantize_byte's word.
+template <bool RAW>
+__device__ __forceinline__ auto quantize_as(float v, float scale)
+{
+  if constexpr (RAW) {
+    return quantize_byte(v, scale);
+  } else {
+    return quantize(v, scale);
+  }
+}
+
 /// Soft demapping of one equalized symbol into QM LLRs (stream order: re, im of bit pair 0, then pair 1, ...),
 /// following the SIMD demappers (demodulation_mapper_qam*.cpp, avx2_helpers.h: reciprocal-width interval index,
 /// separately rounded slope * x + intercept, per-component near-zero masking).
-template <int QM>
-__device__ __forceinline__ void demap(cpx s, float nvar, const demap_pair_table* tab, int* llr)
+/// RAW (llr of uint32_t): only the low byte of each word is the LLR (quantize_byte).
+template <int QM, typename LLR = int>
+__device__ __forceinline__ void demap(cpx s, float nvar, const demap_pair_table* tab, LLR* llr)
 {
 #pragma clang fp contract(off)
+  constexpr bool RAW = !__is_same(LLR, int);
   const float rcp     = (nvar > 0.f) ? 1.f / nvar : 0.f;
   const float part[2] = {s.x, s.y};
   if constexpr (QM == 2) {
     const float g = 2.0f * 1.41421356f;  // 2 * M_SQRT2f32
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      llr[k] = quantize((g * part[k]) * rcp, 120.f / 24.f);
+      llr[k] = quantize_as<RAW>((g * part[k]) * rcp, 120.f / 24.f);
     }
   } else if constexpr (QM == 4) {
     const float a = 0.316227766f;  // 1 / sqrt(10) in float
@@ -82,8 +104,8 @@ __device__ __forceinline__ void demap(cpx s, float nvar, const demap_pair_table*
       const float l01 = (fabsf(x) > 2.f * a) ? 2.f * f - copysignf(0.8f, x) : f;
       const float l23 = 0.8f - fabsf(f);
       const bool  nz  = fabsf(x) <= 1e-9f;
-      llr[k]          = nz ? 0 : quantize(l01 * rcp, 6.f);
-      llr[2 + k]      = nz ? 0 : quantize(l23 * rcp, 6.f);
+      llr[k]          = nz ? 0 : quantize_as<RAW>(l01 * rcp, 6.f);
+      llr[2 + k]      = nz ? 0 : quantize_as<RAW>(l23 * rcp, 6.f);
     }
   } else {
     // Every bit pair but the last shares its interval width and count (2a, 2^(QM/2) intervals; the last: 4a, half as
@@ -104,7 +126,7 @@ __device__ __forceinline__ void demap(cpx s, float nvar, const demap_pair_table*
         const int    idx = (kb == NP - 1) ? idxl : idx0;
         const float2 sl  = *reinterpret_cast<const float2*>(t[kb].piece[idx]);
         const float  l   = (sl.x * x + sl.y) * rcp;
-        llr[2 * kb + k]  = nz ? 0 : quantize(l, 6.f);
+        llr[2 * kb + k]  = nz ? 0 : quantize_as<RAW>(l, 6.f);
       }
     }
   }
@@ -304,8 +326,8 @@ struct lane_stats {
 };
 
 /// Stages the chunk's descrambling words (and the first word of the next chunk) and, for 64/256QAM, the demapper
-/// tables in LDS. The caller synchronises.
-template <int T>
+/// tables in LDS. The caller synchronises. REV: the words bit-reversed, so that bit i of a word belongs to its LLR i.
+template <int T, bool REV>
 __device__ __forceinline__ void stage_chunk(const demod_uniform& u, uint32_t* seq, demap_pair_table* tab)
 {
   const demod_desc& d      = *u.d;
@@ -318,7 +340,8 @@ __device__ __forceinline__ void stage_chunk(const demod_uniform& u, uint32_t* se
   const uint32_t stage = need < DEMOD_CHUNK_WORDS + 1u ? need : DEMOD_CHUNK_WORDS + 1u;
   for (uint32_t j = tid; j < stage; j += T) {
     const uint32_t w = u.word0 + j;
-    seq[j]           = (w < nwords) ? u.gseq[d.seq_word_offset + w] : 0u;
+    const uint32_t v = (w < nwords) ? u.gseq[d.seq_word_offset + w] : 0u;
+    seq[j]           = REV ? __brev(v) : v;
   }
   if (d.qm >= 6) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(u.tables);
@@ -341,34 +364,47 @@ __device__ __forceinline__ void load_re(const demod_desc& d,
                                         uint32_t& sym)
 {
   // Symbol and subcarrier of the RE.
-  uint32_t l = 0;
-#pragma unroll
-  for (int j = 1; j < 15; ++j) {
-    l += (d.sym_cum[j] <= r) ? 1u : 0u;
-  }
-  const uint32_t k = r - d.sym_cum[l];
-  sym              = l;
-  uint32_t       sc;
-  const bool     dm = (d.dmrs_mask >> l) & 1u;
-  if (d.crb_list == DEMOD_CONTIGUOUS) {
-    if (dm) {
-      const uint32_t nd  = d.nd_dmrs;
-      const uint32_t prb = k / nd;
-      sc                 = prb * 12u + static_cast<uint32_t>((d.dmrs_lut >> (4u * (k - prb * nd))) & 15u);
-    } else {
+  uint32_t l = 0, sc;
+  if (d.sym_magic != 0) {
+    // Every data symbol carries sym_res REs and none is a DM-RS symbol (capi_pusch_demod.cpp demod_symbol_form).
+    const uint32_t q = __umulhi(r, d.sym_magic);
+    const uint32_t k = r - __umul24(q, d.sym_res);
+    l = q + d.sym_first + (q >= d.sym_skip_at[0] ? d.sym_skip[0] : 0u) + (q >= d.sym_skip_at[1] ? d.sym_skip[1] : 0u);
+    if (d.crb_list == DEMOD_CONTIGUOUS) {
       sc = k;
+    } else {
+      const uint32_t prb = k / 12u;
+      sc                 = static_cast<uint32_t>(crbs[d.crb_list + prb]) * 12u + (k - prb * 12u);
     }
   } else {
-    // CRB-mask allocation (pusch_demodulator_impl.cpp:290 rb_mask kron the PRB's RE pattern): the p-th allocated
-    // PRB of the symbol is the p-th entry of the transmission's CRB list.
-    const uint32_t per = dm ? static_cast<uint32_t>(d.nd_dmrs) : 12u;
-    const uint32_t prb = k / per;
-    const uint32_t kk  = k - prb * per;
-    sc = static_cast<uint32_t>(crbs[d.crb_list + prb]) * 12u +
-         (dm ? static_cast<uint32_t>((d.dmrs_lut >> (4u * kk)) & 15u) : kk);
+#pragma unroll
+    for (int j = 1; j < 15; ++j) {
+      l += (d.sym_cum[j] <= r) ? 1u : 0u;
+    }
+    const uint32_t k = r - d.sym_cum[l];
+    const bool     dm = (d.dmrs_mask >> l) & 1u;
+    if (d.crb_list == DEMOD_CONTIGUOUS) {
+      if (dm) {
+        const uint32_t nd  = d.nd_dmrs;
+        const uint32_t prb = k / nd;
+        sc                 = prb * 12u + static_cast<uint32_t>((d.dmrs_lut >> (4u * (k - prb * nd))) & 15u);
+      } else {
+        sc = k;
+      }
+    } else {
+      // CRB-mask allocation (pusch_demodulator_impl.cpp:290 rb_mask kron the PRB's RE pattern): the p-th allocated
+      // PRB of the symbol is the p-th entry of the transmission's CRB list.
+      const uint32_t per = dm ? static_cast<uint32_t>(d.nd_dmrs) : 12u;
+      const uint32_t prb = k / per;
+      const uint32_t kk  = k - prb * per;
+      sc = static_cast<uint32_t>(crbs[d.crb_list + prb]) * 12u +
+           (dm ? static_cast<uint32_t>((d.dmrs_lut >> (4u * kk)) & 15u) : kk);
+    }
   }
-  const uint32_t ge = d.grid_base + l * d.nsc + sc;
-  const uint32_t ee = d.ce_base + (d.ce_compact ? 0u : l * d.nsc) + sc;
+  sym               = l;
+  const uint32_t lo = __umul24(l, d.nsc);  // l < 14, nsc <= 3300
+  const uint32_t ge = d.grid_base + lo + sc;
+  const uint32_t ee = d.ce_base + (d.ce_compact ? 0u : lo) + sc;
   // Unsigned 32-bit byte offsets from the buffers' SGPR bases (saddr loads, no 64-bit address arithmetic per load).
   const char* gb = reinterpret_cast<const char*>(grids);
   const char* cb = reinterpret_cast<const char*>(ce);
@@ -421,8 +457,9 @@ __device__ __forceinline__ void setup_uniform(const demod_desc& d, const uint32_
 
 /// Every RE of the chunk owned by this lane: loads, equalization (L layers), demapping (QM bits per layer),
 /// descrambling and the packed LLR bytes into the LDS output buffer. L and QM are compile-time so that every register
-/// array has static indices and the RE's L * QM bytes are assembled in registers.
-template <int L, int QM, bool STATS, int T>
+/// array has static indices and the RE's L * QM bytes are assembled in registers. Where L * QM is a multiple of 4 the
+/// LLRs are descrambled four at a time in a packed word (GENERAL: LLR by LLR, as for every other L * QM).
+template <int L, int QM, bool STATS, int T, bool GENERAL>
 __device__ __forceinline__ void demod_res(demod_uniform        u,
                                           demap_pair_table*    tab,
                                           const uint32_t* __restrict__ grids,
@@ -432,8 +469,9 @@ __device__ __forceinline__ void demod_res(demod_uniform        u,
                                           uint32_t*       seq,
                                           uint32_t*       out32)
 {
-  constexpr uint32_t LQ = L * QM;
-  const demod_desc&  d  = *u.d;
+  constexpr uint32_t LQ    = L * QM;
+  constexpr bool     WORDS = LQ % 4 == 0 && !GENERAL;
+  const demod_desc&  d     = *u.d;
   const uint32_t     P  = d.P;
   const bool         zf = d.eq == DEMOD_EQ_ZF;
   // The first RE's loads are in flight while the chunk's sequence is generated.
@@ -442,7 +480,7 @@ __device__ __forceinline__ void demod_res(demod_uniform        u,
   if (r < u.re_end) {
     load_re<L>(d, r, grids, ce, u.crbs, yw, hw, sym);
   }
-  stage_chunk<T>(u, seq, tab);
+  stage_chunk<T, WORDS>(u, seq, tab);
   // The noise variances and CFO rotations are needed from the first equalisation on: their loads follow the RE's and
   // the sequence's, so the three fly together after the descriptor (chunk -> descriptor -> data, two dependent steps).
   setup_uniform(d, ce, noise_var, rot, u);
@@ -516,28 +554,64 @@ __device__ __forceinline__ void demod_res(demod_uniform        u,
       }
     }
 
-    // Demap, descramble (sequence bits of the RE's LLRs, MSB-first words staged in LDS) and pack the bytes.
+    // Demap, descramble (sequence bits of the RE's LLRs, from the words staged in LDS) and pack the bytes.
     const uint32_t o  = r * LQ - u.word0 * 32u;
     const uint32_t wi = o >> 5;
-    const uint64_t sb = ((static_cast<uint64_t>(seq[wi]) << 32) | seq[wi + 1]) << (o & 31u);
     uint32_t       pk[(LQ + 3) / 4] = {};
     if (STATS && sym != st.sym) {
       st.flush(u.lacc);
       st.sym = sym;
     }
+    if constexpr (WORDS) {
+      // The RE's sequence bits, bit b for LLR b: the staged words are bit-reversed (the shift takes o mod 32).
+      const uint32_t sb = __builtin_amdgcn_alignbit(seq[wi + 1], seq[wi], o);
+      uint32_t       raw[LQ];
 #pragma unroll
-    for (int ly = 0; ly < L; ++ly) {
-      int v[QM];
-      demap<QM>(eq[ly], var[ly], tab, v);
-      if constexpr (STATS) {
-        st.add<QM>(eq[ly], var[ly], v);
+      for (int ly = 0; ly < L; ++ly) {
+        uint32_t rl[QM];
+        demap<QM>(eq[ly], var[ly], tab, rl);
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+          raw[ly * QM + j] = rl[j];
+        }
+        if constexpr (STATS) {
+          int v[QM];
+#pragma unroll
+          for (int j = 0; j < QM; ++j) {
+            v[j] = static_cast<int8_t>(rl[j]);
+          }
+          st.add<QM>(eq[ly], var[ly], v);
+        }
+        // The words this layer completes. Low bytes of four LLRs into a word; 0xff in the bytes whose sequence bit is
+        // set (a selector byte 0x0d of v_perm gives 0xff, 0x0c gives 0); those bytes negated as ~x + 1, the carries
+        // kept inside each byte.
+#pragma unroll
+        for (uint32_t i = ly * QM / 4; 4 * (i + 1) <= (ly + 1) * QM; ++i) {
+          const uint32_t lo   = __builtin_amdgcn_perm(raw[4 * i + 1], raw[4 * i], 0x0c0c0400u);
+          const uint32_t hi   = __builtin_amdgcn_perm(raw[4 * i + 3], raw[4 * i + 2], 0x0c0c0400u);
+          const uint32_t w    = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+          const uint32_t ones = __umul24((sb >> (4 * i)) & 15u, 0x00204081u) & 0x01010101u;
+          const uint32_t m    = __builtin_amdgcn_perm(0u, 0u, ones | 0x0c0c0c0cu);
+          const uint32_t x    = w ^ m;
+          pk[i]               = ((x & 0x7f7f7f7fu) + ones) ^ (x & 0x80808080u);
+        }
       }
+    } else {
+      const uint64_t sb = ((static_cast<uint64_t>(seq[wi]) << 32) | seq[wi + 1]) << (o & 31u);
 #pragma unroll
-      for (int j = 0; j < QM; ++j) {
-        const int      b   = ly * QM + j;
-        const uint32_t bit = static_cast<uint32_t>(sb >> (63 - b)) & 1u;
-        const uint32_t s8  = static_cast<uint8_t>(static_cast<int8_t>(bit ? -v[j] : v[j]));
-        pk[b / 4] |= s8 << (8 * (b % 4));
+      for (int ly = 0; ly < L; ++ly) {
+        int v[QM];
+        demap<QM>(eq[ly], var[ly], tab, v);
+        if constexpr (STATS) {
+          st.add<QM>(eq[ly], var[ly], v);
+        }
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+          const int      b   = ly * QM + j;
+          const uint32_t bit = static_cast<uint32_t>(sb >> (63 - b)) & 1u;
+          const uint32_t s8  = static_cast<uint8_t>(static_cast<int8_t>(bit ? -v[j] : v[j]));
+          pk[b / 4] |= s8 << (8 * (b % 4));
+        }
       }
     }
     const uint32_t ob = (r - u.re_begin) * LQ;
@@ -559,17 +633,17 @@ __device__ __forceinline__ void demod_res(demod_uniform        u,
   }
 }
 
-template <int QM, bool STATS, int T>
+template <int QM, bool STATS, int T, bool GENERAL>
 __device__ __forceinline__ void demod_res_qm(const demod_uniform& u, demap_pair_table* tab,
                                              const uint32_t* __restrict__ grids, const uint32_t* __restrict__ ce,
                                              const float* __restrict__ noise_var, cpx* rot, uint32_t* seq,
                                              uint32_t* out32)
 {
   switch (u.d->L) {
-    case 1: demod_res<1, QM, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    case 2: demod_res<2, QM, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    case 3: demod_res<3, QM, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    default: demod_res<4, QM, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 1: demod_res<1, QM, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 2: demod_res<2, QM, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 3: demod_res<3, QM, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    default: demod_res<4, QM, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
   }
 }
 
@@ -605,8 +679,8 @@ __device__ __forceinline__ void total_stats(const float* v, float* __restrict__ 
 }
 
 /// STATS: also accumulate the post-equalization statistics (a separate instantiation, so that the plain kernel keeps
-/// its register budget).
-template <bool STATS, int T>
+/// its register budget). GENERAL: descrambling and packing LLR by LLR throughout (SRSGPU_OPTION_DEMOD_GENERAL_PATHS).
+template <bool STATS, int T, bool GENERAL = false>
 __global__ __launch_bounds__(T) void pusch_demodulate_kernel(const demod_desc* __restrict__ descs,
                                                                          const mod_chunk* __restrict__ chunks,
                                                                          const demap_pair_table* __restrict__ tables,
@@ -644,10 +718,10 @@ __global__ __launch_bounds__(T) void pusch_demodulate_kernel(const demod_desc* _
   }
 
   switch (d.qm) {
-    case 2: demod_res_qm<2, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    case 4: demod_res_qm<4, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    case 6: demod_res_qm<6, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
-    default: demod_res_qm<8, STATS, T>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 2: demod_res_qm<2, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 4: demod_res_qm<4, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    case 6: demod_res_qm<6, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
+    default: demod_res_qm<8, STATS, T, GENERAL>(u, tab, grids, ce, noise_var, rot, seq, out32); break;
   }
   __syncthreads();
   if (STATS && tid < static_cast<uint32_t>(DEMOD_ACC_PER_TX) && lacc[tid] != 0.f) {
@@ -954,6 +1028,7 @@ void launch_pusch_demodulate(const demod_desc*       d_desc,
                              const mod_chunk*        d_chunks,
                              int                     nof_chunks,
                              int                     plan_threads,
+                             bool                    general,
                              const demap_pair_table* d_tables,
                              const uint32_t*         d_grids,
                              const uint32_t*         d_ch_est,
@@ -972,7 +1047,13 @@ void launch_pusch_demodulate(const demod_desc*       d_desc,
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nof_chunks)), dim3(static_cast<unsigned>(t)), 0, stream,
                        d_desc, d_chunks, d_tables, d_grids, d_ch_est, d_noise_var, d_llrs, d_seq, d_crbs, d_acc);
   };
-  if (d_acc != nullptr) {
+  if (general) {
+    if (d_acc != nullptr) {
+      launch(pusch_demodulate_kernel<true, DEMOD_THREADS, true>, DEMOD_THREADS);
+    } else {
+      launch(pusch_demodulate_kernel<false, DEMOD_THREADS, true>, DEMOD_THREADS);
+    }
+  } else if (d_acc != nullptr) {
     launch(pusch_demodulate_kernel<true, DEMOD_THREADS>, DEMOD_THREADS);
   } else if (threads == 64) {
     launch(pusch_demodulate_kernel<false, 64>, 64);

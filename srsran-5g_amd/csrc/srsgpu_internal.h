@@ -450,8 +450,16 @@ struct demod_desc {
   uint16_t transform_precoding;  ///< Transform-precoded: the demodulate_tp kernel handles the transmission.
   uint16_t cfo_sc;               ///< Subcarrier of the compact row's CFO word relative to ce_base (the first
                                  ///< allocated one: 0 for contiguous allocations, 12 x first CRB for CRB masks).
+  /// Closed form of an RE's symbol, where every symbol with data carries sym_res REs and no DM-RS symbol carries data
+  /// (demod_symbol_form): the RE's data symbol q = (r * sym_magic) >> 32 = r / sym_res is OFDM symbol
+  /// sym_first + q + sum of sym_skip[i] over q >= sym_skip_at[i]. sym_magic = 0: the search through sym_cum.
+  uint32_t sym_magic;       ///< ceil(2^32 / sym_res): exact for r < 2^16 (sym_cum is 16 bits wide).
+  uint16_t sym_res;         ///< REs of a data symbol.
+  uint8_t  sym_first;       ///< First OFDM symbol with data.
+  uint8_t  sym_skip_at[2];  ///< Data symbols in front of an interior run of symbols without data (255: no such run).
+  uint8_t  sym_skip[2];     ///< Length of that run.
 };
-static_assert(sizeof(demod_desc) == 160, "demod_desc layout");
+static_assert(sizeof(demod_desc) == 168, "demod_desc layout");
 constexpr uint32_t DEMOD_CONTIGUOUS = 0xffffffffu;
 
 /// Transform-precoded PUSCH work item: one OFDM symbol of one transmission (M data REs, the inverse DFT length).
@@ -829,6 +837,7 @@ void launch_pusch_demodulate(const demod_desc*        d_desc,
                              const mod_chunk*         d_chunks,
                              int                      nof_chunks,
                              int                      threads,
+                             bool                     general,  ///< LLR-by-LLR packing (256 lanes whatever `threads`)
                              const demap_pair_table*  d_tables,
                              const uint32_t*          d_grids,
                              const uint32_t*          d_ch_est,

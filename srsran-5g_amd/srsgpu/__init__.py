@@ -748,6 +748,7 @@ def load_library(path: str = LIB_PATH):
                                                          ctypes.POINTER(P)]
     lib.srsgpu_pusch_demodulator_plan_nof_llrs.argtypes = [P, ctypes.c_uint32]
     lib.srsgpu_pusch_demodulator_plan_nof_llrs.restype = ctypes.c_uint32
+    lib.srsgpu_pusch_demodulator_plan_symbol_closed_form.argtypes = [P, ctypes.c_uint32]
     lib.srsgpu_pusch_demodulator_plan_execute.argtypes = [P, P, P, P, P, P]
     lib.srsgpu_pusch_demodulator_plan_destroy.argtypes = [P]
     lib.srsgpu_pusch_demodulator_plan_destroy.restype = None
@@ -787,6 +788,7 @@ def load_library(path: str = LIB_PATH):
 EXPORTED_SYMBOLS = [
     "srsgpu_version", "srsgpu_last_error", "srsgpu_context_create", "srsgpu_context_destroy", "srsgpu_context_device",
     "srsgpu_context_set_option", "srsgpu_context_get_option", "srsgpu_pusch_demodulator_plan_scrambling",
+    "srsgpu_pusch_demodulator_plan_symbol_closed_form",
     "srsgpu_ldpc_decoder_plan_create", "srsgpu_ldpc_decoder_plan_execute", "srsgpu_ldpc_decoder_plan_destroy",
     "srsgpu_ldpc_decode", "srsgpu_pusch_cb_plan_create", "srsgpu_pusch_cb_plan_execute",
     "srsgpu_pusch_cb_plan_destroy", "srsgpu_pdsch_encoder_plan_create", "srsgpu_pdsch_encoder_plan_nof_codeblocks",
@@ -899,8 +901,10 @@ OPTION_DECODER_FUSED_DEMATCH = 3  # 1 (default) / 0: every codeblock through the
 OPTION_ENCODER_BYTE_KERNEL = 4    # 0 (default) / 1: the byte-per-bit encoder kernel for every codeblock
 OPTION_ENCODER_ZERO_OUTPUT = 5    # 0 (default) / 1: the encoder always clears its output first
 OPTION_DECODER_TB_FOLD = 6        # 1 (default) / 0: single-codeblock TBs always through the separate TB stage
+OPTION_DEMOD_GENERAL_PATHS = 7    # 0 (default) / 1: the demodulator's symbol search and LLR-by-LLR packing throughout
 OPTION_DEFAULTS = {OPTION_DECODER_SPLIT: -1, OPTION_DECODER_PAIRS: 0, OPTION_DECODER_FUSED_DEMATCH: 1,
-                   OPTION_ENCODER_BYTE_KERNEL: 0, OPTION_ENCODER_ZERO_OUTPUT: 0, OPTION_DECODER_TB_FOLD: 1}
+                   OPTION_ENCODER_BYTE_KERNEL: 0, OPTION_ENCODER_ZERO_OUTPUT: 0, OPTION_DECODER_TB_FOLD: 1,
+                   OPTION_DEMOD_GENERAL_PATHS: 0}
 
 
 class _Handle:
@@ -2592,6 +2596,10 @@ class PuschDemodulatorPlan(_Handle):
 
     def nof_llrs(self, tx: int) -> int:
         return int(_lib.srsgpu_pusch_demodulator_plan_nof_llrs(self.handle, tx))
+
+    def symbol_closed_form(self, tx: int) -> bool:
+        """The plan finds the OFDM symbol of transmission `tx`'s REs by the closed form, not by the search."""
+        return bool(_lib.srsgpu_pusch_demodulator_plan_symbol_closed_form(self.handle, tx))
 
     def execute(self, d_grids, d_ch_est, d_noise_var, d_llrs, stream=None, d_stats=None):
         """d_stats: optional float32 device buffer of DEMOD_STATS floats per transmission (SINR dB / EVM rows)."""

@@ -106,6 +106,21 @@ def pdsch_encoder_cases():
         mo += ncb
 
 
+def pdsch_encoder_regime_codewords():
+    """(keys (n, 8): bg, Z, TB bytes, rv, Qm, symbols, Nref, codeword bits; [codeword bits]) made by the reference's
+    segmenter, encoder and rate matcher on the regime grid of tests/pdsch_encoder_regime_cases.py at its GOLDEN_Z
+    lifting sizes, then on its multi-codeblock list (tools/gen_golden.py gen_pdsch_encoder_regimes). The TBs are the
+    case module's own (transport_block)."""
+    d = _load("pdsch_encoder_regimes.npz")
+    keys, packed = d["keys"].astype(np.int64), d["codewords"]
+    out, o = [], 0
+    for nbits in keys[:, -1]:
+        nbytes = (int(nbits) + 7) // 8
+        out.append(np.unpackbits(packed[o:o + nbytes])[:nbits])
+        o += nbytes
+    return keys, out
+
+
 def pdsch_modulator_cases():
     """Yields (cfg dict, nof_bits, grid_nof_prb, weights (P x L complex64), packed codeword, grid uint16
     (P, 14, 12 * grid_nof_prb, 2)) made by the reference's pdsch_modulator_impl."""

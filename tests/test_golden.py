@@ -82,6 +82,26 @@ def test_pdsch_encoder_golden(orc):
     assert n == 14
 
 
+def test_pdsch_encoder_regimes_golden(orc):
+    """The oracle composition against the reference's recorded codewords on the encoder regime grid's fixture subset
+    (ten lifting sizes per base graph with Z = 2, 3, 7, 15, 32, 64, 208 and 384 among them, every class of the grid)
+    and on its multi-codeblock list; the fixture's rows are the case module's own cases."""
+    import pdsch_encoder_regime_cases as R
+    grid = R.build_grid()
+    cases = [grid[i] for i in R.golden_subset(grid)] + R.build_multi()
+    keys, want = G.pdsch_encoder_regime_codewords()
+    assert np.array_equal(keys, np.array([R.key_numbers(c) for c in cases], np.int64))
+    for bg in (1, 2):
+        # Z = 2 and 3 are no BG2 shapes.
+        assert {c["Z"] for c in cases if c["bg"] == bg} >= {2, 3, 7, 15, 32, 64, 208, 384} - ({2, 3} if bg == 2 else set())
+        assert len(R.GOLDEN_Z[bg]) == 10
+    reached = set()
+    for c, w in zip(cases, want):
+        assert np.array_equal(R.expected(orc, c), w), R.key(c)
+        reached |= {cls for cls, hit in R.census(c).items() if hit is True}
+    assert reached >= set(R.CLASSES)
+
+
 def test_pdsch_modulator_golden(orc):
     n = 0
     for cfg, nbits, grid_prb, w, cw, grid in G.pdsch_modulator_cases():

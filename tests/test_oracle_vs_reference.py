@@ -161,6 +161,29 @@ def test_rate_match(orc, ref, case):
     assert np.array_equal(orc.rate_match(bg, Z, rv, qm, Nref, nof_filler, cb, E), want)
 
 
+# Cases of the encoder's regime grid that the reference refuses, with the reason: (key, reason). None so far.
+ENCODER_REGIME_REFUSED = []
+
+
+@pytest.mark.parametrize("which", ["grid", "multi"])
+def test_pdsch_encoder_regime_grid_matches_reference(orc, ref, which):
+    """The encoder's regime grid and its multi-codeblock list (tests/pdsch_encoder_regime_cases.py): every lifting size
+    of a one-codeblock TB at every rv, buffer kind and Qm, lengths on each side of the wrap, of the filler range and of
+    the lifted columns. The reference's segmenter, generic encoder and rate matcher against the oracle composition the
+    GPU tests expect (chain_lib.oracle_pdsch_encode), bit for bit. At most 2 % of the cases may be listed as refused."""
+    import pdsch_encoder_regime_cases as R
+    cases, want = R.grid_with_expected(orc) if which == "grid" else R.multi_with_expected(orc)
+    refused = {k for k, _ in ENCODER_REGIME_REFUSED}
+    assert len(refused) <= len(cases) // 50
+    for c, w in zip(cases, want):
+        if R.key(c) in refused:
+            continue
+        cw, meta = ref.pdsch_encode(c["bg"], c["rv"], c["qm"], c["layers"], c["Nref"], c["nsym"], R.transport_block(c))
+        assert meta.shape[0] == c.get("codeblocks", 1) and meta[0, 0] == c["Z"], R.key(c)
+        assert [int(m[1]) for m in meta] == [R.census(c, i)["filler"] for i in range(meta.shape[0])], R.key(c)
+        assert np.array_equal(cw, w), R.key(c)
+
+
 @pytest.mark.parametrize("case", _rm_cases())
 def test_rate_dematch(orc, ref, case):
     bg, Z, rv, qm, Nref, nof_filler, E = case

@@ -87,23 +87,25 @@ def cases():
     return out
 
 
-def _encode_plan(ctx, tbs, cfgs, tb_mod4, gap):
-    """One plan over all TBs: TB i at a byte offset congruent to tb_mod4[i] modulo 4 (random bytes between TBs),
-    codewords `gap` bytes apart in an output pre-filled with 0xAB. Returns the unpacked codewords, the output bytes
-    and the codewords' byte ranges."""
+def _encode_plan(ctx, tbs, cfgs, tb_mod4, gap, tb_tail=16):
+    """One plan over all TBs: TB i at a byte offset congruent to tb_mod4[i] modulo 4 (random bytes between TBs and
+    `tb_tail` of them behind the last), codewords `gap` bytes apart, each at the next multiple of 4 bytes, in an output
+    pre-filled with 0xAB. Returns the unpacked codewords (a last byte's spare bits cut off), the output bytes and the
+    codewords' byte ranges."""
     import srsgpu
     import torch
     arr, _, _, _ = srsgpu.make_pdsch_configs([t.size for t in tbs], cfgs)
     to = co = 0
-    ranges = []
+    ranges, nbits = [], []
     for a, t, c, m in zip(arr, tbs, cfgs, tb_mod4):
         to = (to + 3) // 4 * 4 + m
         a.tb_offset, a.cw_offset = to, co
-        nbytes = c.nof_ch_symbols * c.modulation_order // 8
+        nbits.append(c.nof_ch_symbols * c.modulation_order)
+        nbytes = (nbits[-1] + 7) // 8
         ranges.append((co, co + nbytes))
         to += t.size
-        co += nbytes + gap
-    buf = np.random.default_rng(5).integers(0, 256, to + 16).astype(np.uint8)
+        co = (co + nbytes + gap + 3) // 4 * 4
+    buf = np.random.default_rng(5).integers(0, 256, to + tb_tail).astype(np.uint8)
     for a, t in zip(arr, tbs):
         buf[a.tb_offset: a.tb_offset + t.size] = t
     dev = torch.device("cuda", ctx.device)
@@ -114,7 +116,7 @@ def _encode_plan(ctx, tbs, cfgs, tb_mod4, gap):
     torch.cuda.synchronize(dev)
     plan.close()
     raw = d_cw.cpu().numpy()
-    return [np.unpackbits(raw[b:e]) for b, e in ranges], raw, ranges
+    return [np.unpackbits(raw[b:e])[:n] for (b, e), n in zip(ranges, nbits)], raw, ranges
 
 
 @pytest.mark.parametrize("mode", ["tiled", "gaps"])

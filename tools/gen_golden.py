@@ -183,6 +183,23 @@ def gen_pdsch_encoder(ref, rng):
                         cw=np.concatenate(cws), meta=np.concatenate(metas))
 
 
+def gen_pdsch_encoder_regimes(ref, rng):
+    """The reference's codewords (segmenter, generic encoder, rate matcher) of the encoder's regime grid
+    (tests/pdsch_encoder_regime_cases.py) at the lifting sizes GOLDEN_Z, then of its multi-codeblock list. Rows of
+    `keys`: bg, Z, TB bytes, rv, Qm, symbols, Nref, codeword bits; `codewords`: each packed to whole bytes. The TBs are
+    seeded by the case module, so only the outputs are stored."""
+    import pdsch_encoder_regime_cases as R
+    grid = R.build_grid()
+    cases = [grid[i] for i in R.golden_subset(grid)] + R.build_multi()
+    keys, cws = [], []
+    for c in cases:
+        cw, _ = ref.pdsch_encode(c["bg"], c["rv"], c["qm"], c["layers"], c["Nref"], c["nsym"], R.transport_block(c))
+        keys.append(R.key_numbers(c))
+        cws.append(np.packbits(cw))
+    save_npz_fixed(os.path.join(OUT, "pdsch_encoder_regimes.npz"), keys=np.array(keys, np.int32),
+                   codewords=np.concatenate(cws))
+
+
 def gen_pdsch_modulator(ref, rng):
     from oracle_lib import PDSCH_MOD_KEYS
     from pdsch_mod_cases import random_config
@@ -470,7 +487,8 @@ def main():
         for name in sys.argv[1:]:
             seed = {"ofdm": 16, "pusch_demod": 17, "pusch_chest": 18, "pdsch_dmrs": 19, "pusch_chest_cfo": 20,
                     "pdsch_mod_general": 21, "pdsch_dmrs_mask": 22, "pusch_demod_general": 23, "ulsch_demux": 24, "pusch_chest_low_papr": 25,
-                    "pusch_chest_273": 26, "ldpc_decoder_regimes": 27}[name]
+                    "pusch_chest_273": 26, "ldpc_decoder_regimes": 27,
+                    "pdsch_encoder_regimes": 28}[name]
             globals()["gen_" + name](ref, np.random.default_rng(seed))
         return
     gen_crc(ref, np.random.default_rng(10))
@@ -491,6 +509,7 @@ def main():
     gen_pusch_chest_low_papr(ref, np.random.default_rng(25))
     gen_pusch_chest_273(ref, np.random.default_rng(26))
     gen_ldpc_decoder_regimes(ref, np.random.default_rng(27))
+    gen_pdsch_encoder_regimes(ref, np.random.default_rng(28))
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

@@ -41,7 +41,7 @@ def run_case(ctx, lib, name, ests, grid):
     torch.cuda.synchronize()
     njobs = 4 * len(ests)
     buf = np.zeros(4096 * SLOTS, dtype=np.uint64)
-    assert lib.srsgpu_debug_chest_profile(buf.ctypes.data_as(srsgpu.ctypes.c_void_p), buf.size) == 0
+    assert lib.srsgpu_debug_chest_profile(buf.ctypes.data, buf.size) == 0
     st = buf.reshape(4096, SLOTS)[:njobs].astype(np.int64)
     d = np.diff(st[:, :8], axis=1)
     wall_us = (st[:, 11] - st[:, 10]) / 100.0

@@ -11,7 +11,6 @@ Each codeblock's workgroup stamps s_memtime at: start (0), after the LLR load (1
 number of layers (31). Prints per-phase average cycles and the kernel-wide concurrency picture.
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -77,7 +76,6 @@ def main():
 
     n = min(cb_total, 4096)
     buf = np.zeros(n * SLOTS, dtype=np.uint64)
-    lib.srsgpu_debug_decoder_profile.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int]
     # Even lifting sizes run on the packed kernel (its own stamp array); fall back to the one-row kernel's.
     assert lib.srsgpu_debug_decoder_profile(buf.ctypes.data, buf.size, 1) == 0
     if not buf.any():

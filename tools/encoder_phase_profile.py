@@ -12,7 +12,6 @@ after the CB CRC (3), after the message words (4), after the core rows (5), afte
 rows (7), after rate matching (8); s_memrealtime (100 MHz) at start / end (9 / 10).
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -59,7 +58,6 @@ def main():
     ncb = sum(s.nof_segments for s in segs) * S
     n = min(ncb, 8192)
     buf = np.zeros(n * SLOTS, dtype=np.uint64)
-    lib.srsgpu_debug_encoder_profile.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     assert lib.srsgpu_debug_encoder_profile(buf.ctypes.data, buf.size) == 0
     p = buf.reshape(n, SLOTS).astype(np.int64)
     ok = (p[:, 10] > p[:, 9]) & (p[:, 8] >= p[:, 0])
